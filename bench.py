@@ -8,6 +8,14 @@ One "step" = zero_grad -> forward -> backward -> (RCCL gradient all-reduce when 
 already resident in HBM.  Primary workload: CVC-YOLOv3 (yolo_baseline topology) 416x416, classes=80, bf16, 32 images per GPU
 (BASELINE.json configs[2]/[3]); secondary workload reported in the same JSON line: RektNet 80x80 bf16, 256 images per GPU
 (configs[1]).  Weak scaling: per-GPU batch fixed.  Rank 0 prints ONE JSON line.
+
+A plain run times the primary workload only (YOLOv3 unless --workload names another): set-up, warm-up, the --steps timed steps, the
+outputs (--dump-outputs DIR) and the line.  --full adds everything else the line and bench_detail.json carry: the secondary workloads,
+CPU baselines, the fp32 and classes=1 rates, the host-copy and unchanged-loop legs, per-kernel breakdown and roofline, measured peaks,
+and on N > 1 ranks the replica check and the reducer-detached step.
+
+  python bench.py --gpus 1 --steps K --warmup W --full
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # DIR/<name>.npy: what the last timed step computed
 """
 import argparse
 import contextlib
@@ -99,6 +107,28 @@ def timed_region(fn, steps, warmup, device, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_SAMPLE = 1 << 21        # elements kept of a larger output (same seeded positions every run)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every tensor of `arrays` ({name: tensor}) as dirname/<name>.npy, float64 where the tensor is float64 or an int64
+    index, else float32.  An output of more than DUMP_SAMPLE elements is flattened and sampled at seeded positions (sorted, duplicates
+    dropped), so two builds given the same arguments write comparable files."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        v = t.detach()
+        if v.numel() > DUMP_SAMPLE:
+            pos = np.unique(np.random.default_rng(0).integers(0, v.numel(), DUMP_SAMPLE))
+            v = v.reshape(-1)[torch.from_numpy(pos).to(v.device)]
+        v = v.to(torch.float64 if v.dtype in (torch.float64, torch.int64) else torch.float32).cpu().numpy()
+        total += v.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(dirname, name + ".npy"), v)
 
 
 def conv_flops(args):
@@ -684,6 +714,8 @@ def main():
     ap.add_argument("--no-fp32", action="store_true", help="skip the same-precision-as-the-reference (fp32 kernels) YOLOv3 rate")
     ap.add_argument("--no-ref-loop", action="store_true", help="skip the legs that time the reference's unchanged training-loop statements")
     ap.add_argument("--no-classes1", action="store_true", help="skip the classes=1 (cone-realistic, 18-channel heads) YOLOv3 rate")
+    ap.add_argument("--full", action="store_true", help="also run every secondary workload, baseline, check and breakdown (the --no-* flags trim it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     a = ap.parse_args()
     global CPU_THREADS
     if a.cpu_threads:
@@ -705,8 +737,11 @@ def main():
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
             sk.close()
-            os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
-                                      "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+            # a child process, not exec: this process has already opened the GPU (device_count above)
+            import subprocess
+            rc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
+                                 "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]).returncode
+            raise SystemExit(rc)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -731,8 +766,13 @@ def main():
     detail = {}            # per-kernel tables: written to bench_detail.json, NOT into the one line the driver parses
     tmp = tempfile.mkdtemp(prefix="mdcv_bench_")
     cfg = write_yolo_cfg(tmp, classes=a.yolo_classes)
+    primary = a.workload if a.workload in ("rektnet", "postprocess", "joint") else "yolo"
+    dump = a.dump_outputs if rank == 0 else ""
 
-    if a.workload in ("both", "yolo"):
+    def runs(workload):                                        # a plain run times the primary workload alone
+        return workload == primary or (a.full and a.workload == "both")
+
+    if runs("yolo"):
         cwd = os.getcwd()
         os.chdir(tmp)
         try:
@@ -749,21 +789,27 @@ def main():
         x = torch.rand(B, 3, 416, 416, generator=g).to(device)
         tg = synth_targets(B, 16, g).to(device)
 
+        last = {}
+
         def yolo_step():
             opt.zero_grad()
             out = net(x, tg)
             out[0].sum().backward()
             red.finish()
             opt.step()
+            last["out"] = out
             return out
         dt = timed_region(yolo_step, a.steps, a.warmup, device, world)
         ips = B * world * a.steps / dt
+        if dump:                          # the 7 loss terms, then samples of the updated fp32 parameters and of the step's gradients
+            pflat, gflat = net.flat_parameters()
+            dump_outputs(dump, {"yolo_losses": torch.stack([v.reshape(()) for v in last["out"]]), "yolo_params": pflat, "yolo_grads": gflat})
         comm = red.pop_comm_stats()                            # averaged over the warm-up and the timed steps
         red.timing = False
-        loss = float(yolo_step()[0])
+        loss = float(yolo_step()[0]) if a.full else None
         result = {"ms_per_step": 1e3 * dt / a.steps, "value": ips}
         pcie = None
-        if a.host_input or (world == 1 and not a.no_ref_loop):   # what train.py's loop does with a DataLoader batch: pinned host tensors, .to(device, non_blocking=True)
+        if a.host_input or (a.full and world == 1 and not a.no_ref_loop):   # what train.py's loop does with a DataLoader batch: pinned host tensors, .to(device, non_blocking=True)
             # (part of the default N = 1 line since round 6: VERDICT r5 found the field null in the driver's line; --host-input forces it for N > 1)
             xh, th = x.cpu().pin_memory(), tg.cpu().pin_memory()
 
@@ -778,22 +824,23 @@ def main():
             dth = timed_region(yolo_step_h2d, a.steps, a.warmup, device, world)
             pcie = B * world * a.steps / dth
         unchanged = None
-        if world == 1 and not a.no_ref_loop:
+        if a.full and world == 1 and not a.no_ref_loop:
             # the loop the drop-in promises to leave unchanged, on the same model (its parameters are views of the flat buffers either way)
             unchanged = reference_loop_yolo(net, device, x.cpu().pin_memory(), tg.cpu().pin_memory(), max(5, min(20, a.steps)), 3)
         extra["yolo"] = {"images_per_sec_with_h2d_copy": pcie, "unchanged_loop_images_per_sec": unchanged, "images_per_sec": ips, "ms_per_step": 1e3 * dt / a.steps, "global_batch": B * world, "final_loss": loss,
                          "mfma_frac_step": ips * (YOLO_TRAIN_GFLOP_PER_IMG if a.yolo_classes == 80 else 195.87) / 1e3 / (PEAK_BF16_TFLOPS * world)}
-        if world > 1:                 # replicas must hold identical parameters after the reduced-gradient updates
-            chk = net.flat_parameters()[0].double().sum().reshape(1)
-            lo, hi = chk.clone(), chk.clone()
-            dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-            extra["yolo"]["replicas_in_sync"] = bool((hi - lo).abs().item() <= 1e-6 * max(1.0, abs(hi.item())))
+        if world > 1:
+            if a.full:                # replicas must hold identical parameters after the reduced-gradient updates
+                chk = net.flat_parameters()[0].double().sum().reshape(1)
+                lo, hi = chk.clone(), chk.clone()
+                dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+                dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+                extra["yolo"]["replicas_in_sync"] = bool((hi - lo).abs().item() <= 1e-6 * max(1.0, abs(hi.item())))
             extra["yolo"]["comm"] = dict(comm or {}, **(preflight or {}), backend="rccl" if backend == "nccl" else backend, ranks=dist.get_world_size(),
                                          gradient_bytes=int(net.flat_parameters()[1].numel() * 4), bucket_mb=32.0)
             # allreduce_busy_ms = time the comm stream spent inside all-reduce calls per step; exposed_comm_ms = how long after the last
             # compute kernel of backward the last bucket finished (rank 0, HIP events)
-        if not a.no_breakdown:        # every rank runs the instrumented steps (they contain the collective); rank 0 reports
+        if a.full and not a.no_breakdown:        # every rank runs the instrumented steps (they contain the collective); rank 0 reports
             plan = [p for p in net._plans.values() if p.has_bwd][0]
             in_step = in_step_kernel_times(yolo_step)            # live, inside normal two-stream steps
             rec, krec = kernel_breakdown(net, plan, yolo_step)   # one serial step: work per launch + kernel-alone durations
@@ -812,7 +859,7 @@ def main():
                 detail["yolo_roofline_kernels"] = rows
                 if traffic:
                     extra["yolo"]["hbm_bytes_per_step"] = traffic.get("total_bytes_per_step")
-        if world > 1:
+        if a.full and world > 1:
             # the number that decides the exchange design on hardware: the same step on the same ranks with the reducer DETACHED (no
             # all-reduce; replicas diverge from here on, so this runs last).  stretch = attached / detached.
             net._dp_reducer = None
@@ -825,7 +872,7 @@ def main():
             dtd = timed_region(yolo_step_local, nd, 3, device, world)
             extra["yolo"]["comm"]["ms_per_step_reducer_detached"] = 1e3 * dtd / nd
             extra["yolo"]["comm"]["step_stretch_with_reducer"] = (dt / a.steps) / (dtd / nd)
-        if world == 1 and a.precision == "bf16" and not a.no_fp32 and a.workload in ("both", "yolo"):
+        if a.full and world == 1 and a.precision == "bf16" and not a.no_fp32:
             # the reference computes in fp32: the same step with the fp32 kernels (exact-f32 MFMA), reported beside the bf16 value
             del opt
             net._plans.clear()
@@ -852,7 +899,7 @@ def main():
             opt = None
         del net, opt
         torch.cuda.empty_cache()
-        if world == 1 and a.yolo_classes == 80 and a.precision == "bf16" and not a.no_classes1:
+        if a.full and world == 1 and a.yolo_classes == 80 and a.precision == "bf16" and not a.no_classes1:
             # "also report classes=1" -- the cone-realistic variant (18-channel heads, models.py:51-54), same step, same batch
             cfg1 = write_yolo_cfg(tempfile.mkdtemp(prefix="mdcv_bench_c1_"), classes=1)
             cwd = os.getcwd()
@@ -874,7 +921,7 @@ def main():
             del net1, opt1
             torch.cuda.empty_cache()
 
-    if a.workload in ("both", "rektnet"):
+    if runs("rektnet"):
         torch.manual_seed(0)
         kp = KeypointNet(7, (80, 80), precision=a.precision).to(device).train()
         with contextlib.redirect_stdout(sys.stderr):           # the reference's constructor prints its configuration
@@ -886,6 +933,8 @@ def main():
         x = torch.rand(B, 3, 80, 80, generator=g).to(device)
         tp = (torch.rand(B, 7, 2, generator=g) * (79 / 80)).to(device)
 
+        last = {}
+
         def rekt_step():
             opt.zero_grad()
             hm, pts = kp(x)
@@ -893,18 +942,23 @@ def main():
             loss.backward()
             red.finish()
             opt.step()
+            last["out"] = (hm, pts, loss)
             return loss
         dt = timed_region(rekt_step, a.steps, a.warmup, device, world)
         ips = B * world * a.steps / dt
+        if dump and primary == "rektnet":
+            hm, pts, loss = last["out"]
+            pflat, gflat = kp.flat_parameters()
+            dump_outputs(dump, {"rektnet_loss": loss.reshape(1), "rektnet_pts": pts, "rektnet_hm": hm, "rektnet_params": pflat, "rektnet_grads": gflat})
         extra["rektnet"] = {"images_per_sec": ips, "ms_per_step": 1e3 * dt / a.steps, "global_batch": B * world,
-                            "final_loss": float(rekt_step()),
+                            "final_loss": float(rekt_step()) if a.full else None,
                             "mfma_frac_step": ips * REKT_TRAIN_GFLOP_PER_IMG / 1e3 / (PEAK_BF16_TFLOPS * world),
                             "hbm_frac_step": ips * REKT_TRAIN_MB_PER_IMG / 1e3 / (PEAK_HBM_GBS * world)}
-        if world == 1 and not a.no_ref_loop:
+        if a.full and world == 1 and not a.no_ref_loop:
             with contextlib.redirect_stdout(sys.stderr):
                 extra["rektnet"]["unchanged_loop_images_per_sec"] = reference_loop_rektnet(
                     kp, crit, device, x.cpu(), torch.zeros(B, 7, 80, 80), tp.cpu(), max(5, min(20, a.steps)), 3)
-        if not a.no_breakdown:
+        if a.full and not a.no_breakdown:
             plan = [p for p in kp._plans.values() if p.has_bwd][0]
             in_step = in_step_kernel_times(rekt_step)
             rec, krec = kernel_breakdown(kp, plan, rekt_step)
@@ -922,10 +976,10 @@ def main():
                     result_roof = top
         if a.workload == "rektnet":
             result = {"ms_per_step": 1e3 * dt / a.steps, "value": ips}
-            if not a.no_breakdown and top:
+            if a.full and not a.no_breakdown and top:
                 result["roofline"] = result_roof
 
-    if a.workload in ("both", "postprocess"):
+    if runs("postprocess"):
         # validate.py's per-image loop for one batch of eval outputs [B, 10647, 85] (416^2, 80 classes),
         # thresholds of yolo_baseline.cfg:17-20.  Images are independent: ranks shard them, no collective.
         from mdcv.yolo.postprocess import detect_postprocess
@@ -933,11 +987,15 @@ def main():
         out_np, tg_np = synth_eval_output(B, N, C, T, 3000 + rank)
         outp, tgp = torch.from_numpy(out_np).to(device), torch.from_numpy(tg_np).to(device)
 
+        last = {}
+
         def post_step():
-            return detect_postprocess(outp, tgp, 0.8, 0.25, 0.5, 416, 416)
-        dt = timed_region(post_step, max(a.steps, 50), a.warmup, device, world)
-        nst = max(a.steps, 50)
-        det = post_step()
+            last["det"] = detect_postprocess(outp, tgp, 0.8, 0.25, 0.5, 416, 416)
+        nst = a.steps if primary == "postprocess" else max(a.steps, 50)        # a ~0.1 ms step rides along with at least 50
+        dt = timed_region(post_step, nst, a.warmup, device, world)
+        det = last["det"]
+        if dump and primary == "postprocess":
+            dump_outputs(dump, {"post_" + k: getattr(det, k) for k in ("boxes", "prob", "cls", "index", "correct", "count", "stats")})
         extra["postprocess"] = {"images_per_sec": B * world * nst / dt, "ms_per_batch": 1e3 * dt / nst, "batch_per_gpu": B,
                                 "rows_per_image": N, "classes": C, "kept_mean": float(det.count.float().mean()),
                                 "mean_ap": float(det.stats[det.stats[:, 3] > 0, 0].mean()),
@@ -946,10 +1004,10 @@ def main():
                                 "hbm_floor_us": B * N * 64 / (PEAK_HBM_GBS * 1e9) * 1e6}
         if a.workload == "postprocess":
             result = {"ms_per_step": 1e3 * dt / nst, "value": B * world * nst / dt}
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
             extra["postprocess"]["cpu_baseline"] = cpu_baseline_post(out_np, tg_np)
 
-    if a.workload in ("joint", "both"):
+    if runs("joint"):
         # BASELINE.json configs[4]: YOLOv3 608x608 detect -> batched RektNet crops; frames are independent, ranks shard them.
         # A random-init detector in eval mode outputs a near-constant confidence (~0.5), so nothing passes conf 0.8.  The
         # detector forward is run and timed for real; its output then gets synthetic cone detections written into a few rows
@@ -1002,30 +1060,42 @@ def main():
                 return o
         det_net = Seeded(net).eval()
         thr = 0.8
-        with torch.no_grad():
-            out0 = det_net(x)
+        if a.full:
+            with torch.no_grad():
+                out0 = det_net(x)
         pipe = JointPipeline(det_net, kp, conf_thres=thr, nms_thres=0.25, max_cones=16, bucket=64)
         stages = {}
+        last = {}
 
         def stage(name, fn, n=None):
             n = n or a.steps
             stages[name] = 1e3 * timed_region(fn, n, a.warmup, device, world) / n
+
+        def pipe_step():
+            last["res"] = pipe(x, frames=x8)
         with torch.no_grad():
-            stage("detector_eval_608", lambda: det_net(x))
-            det = detect_postprocess(out0, None, thr, 0.25, 0.5, 608, 608)
-            stage("postprocess", lambda: detect_postprocess(out0, None, thr, 0.25, 0.5, 608, 608))
-            # crops are cut from the uint8 frames with the reference's rule: 8-bit fixed-point cv2.resize, then / 255 (RektNet/dataset.py:35-38,52)
-            crops, _, M = crop_resize(x8, det.boxes[:, :16], det.count, (80, 80), pad_rows_to=64)
-            stage("crop_resize", lambda: crop_resize(x8, det.boxes[:, :16], det.count, (80, 80), pad_rows_to=64))
-            stage("keypoint_eval", lambda: kp(crops))
-            dt = timed_region(lambda: pipe(x, frames=x8), a.steps, a.warmup, device, world)
+            if a.full:                         # each stage timed alone first
+                stage("detector_eval_608", lambda: det_net(x))
+                det = detect_postprocess(out0, None, thr, 0.25, 0.5, 608, 608)
+                stage("postprocess", lambda: detect_postprocess(out0, None, thr, 0.25, 0.5, 608, 608))
+                # crops are cut from the uint8 frames with the reference's rule: 8-bit fixed-point cv2.resize, then / 255 (RektNet/dataset.py:35-38,52)
+                crops, _, M = crop_resize(x8, det.boxes[:, :16], det.count, (80, 80), pad_rows_to=64)
+                stage("crop_resize", lambda: crop_resize(x8, det.boxes[:, :16], det.count, (80, 80), pad_rows_to=64))
+                stage("keypoint_eval", lambda: kp(crops))
+            dt = timed_region(pipe_step, a.steps, a.warmup, device, world)
         ips = B * world * a.steps / dt
+        res = last["res"]
+        if not a.full:
+            det, M = res["det"], res["num"]
+        if dump and primary == "joint":
+            dump_outputs(dump, {**{"joint_det_" + k: getattr(res["det"], k) for k in ("boxes", "prob", "cls", "index", "count")},
+                                **{"joint_" + k: res[k] for k in ("crops", "owner", "keypoints", "keypoints_frame") if res[k] is not None}})
         extra["joint"] = {"images_per_sec": ips, "ms_per_batch": 1e3 * dt / a.steps, "frames_per_gpu": B, "crops_per_batch": M,
                           "crop_rule": "uint8 frame -> cv2 8-bit fixed-point INTER_LINEAR -> /255 (mdcv_crop_resize_u8)",
                           "conf_thres": thr, "kept_per_frame_mean": float(det.count.float().mean()), "stage_ms": {k: round(v, 4) for k, v in stages.items()},
                           "stage_images_per_sec": {k: round(B * world / (v * 1e-3), 1) for k, v in stages.items()}}
         jres = {"ms_per_step": 1e3 * dt / a.steps, "value": ips}
-        if not a.no_breakdown:
+        if a.full and not a.no_breakdown:
             def joint_step():
                 with torch.no_grad():
                     pipe(x, frames=x8)
@@ -1057,9 +1127,8 @@ def main():
             torch.cuda.empty_cache()
 
     if rank == 0:
-        primary = a.workload if a.workload in ("rektnet", "postprocess", "joint") else "yolo"
         cb = None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cb = (cpu_baseline_yolo(cfg, tmp) if primary == "yolo" else cpu_baseline_rektnet() if primary == "rektnet"
                   else extra["postprocess"].pop("cpu_baseline", None) if primary == "postprocess" else cpu_baseline_joint(cfg, tmp))
             if a.workload == "both":
@@ -1071,9 +1140,11 @@ def main():
                     detail["postprocess_cpu_baseline"] = pb
                     extra["postprocess"]["cpu_images_per_sec"] = pb["value"]
         line = build_line(a, world, primary, result, extra, cb)
-        detail["peaks"] = measured_peaks()
-        line["peaks"] = {k: detail["peaks"].get(k) for k in ("measured_peak_tflops", "measured_hbm_gbs")}
-        detail_path = write_detail(line, extra, detail)
+        detail_path = None
+        if a.full:
+            detail["peaks"] = measured_peaks()
+            line["peaks"] = {k: detail["peaks"].get(k) for k in ("measured_peak_tflops", "measured_hbm_gbs")}
+            detail_path = write_detail(line, extra, detail)
         line["detail"] = os.path.relpath(detail_path, ROOT) if detail_path else None
         print(json.dumps(compact(line)))
     if rank == 0 and a.dump_launches:

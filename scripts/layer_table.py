@@ -1,4 +1,4 @@
-"""Per-launch table of a workload's conv kernels from `bench.py --dump-launches` (serial HIP-event times of one instrumented step).
+"""Per-launch table of a workload's conv kernels from `bench.py --full --dump-launches` (serial HIP-event times of one instrumented step).
 usage: layer_table.py dump.json > table.txt"""
 import collections
 import json

@@ -384,7 +384,7 @@ def test_bench_gpus_flag_is_honoured():
                          cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and "disagree" in (out.stderr + out.stdout)
     out = subprocess.run([sys.executable, bench, "--gpus", "2", "--workload", "yolo", "--yolo-batch", "4", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-breakdown"], env=dict(env, MDCV_DIST_BACKEND="gloo"), cwd=ROOT, capture_output=True,
+                          "--full", "--no-cpu-baseline", "--no-breakdown"], env=dict(env, MDCV_DIST_BACKEND="gloo"), cwd=ROOT, capture_output=True,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1054,13 +1054,37 @@ def test_bench_two_ranks_on_one_gpu_keep_replicas_in_sync():
     env = dict(os.environ, MDCV_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "yolo", "--yolo-batch", "4",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-breakdown"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-breakdown"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "dp2" and line["config"]["global_batch"] == 8
     assert line["workloads"]["yolo"]["replicas_in_sync"] is True
     assert line["value"] > 0
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` run times the headline YOLOv3 step alone (no secondary workload, baseline or breakdown) for exactly --steps
+    steps, and --dump-outputs writes what its last timed step computed: the seven loss terms and samples of the updated parameters and
+    of the gradients, float32, 64 MB at most."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MDCV_DIST_BACKEND")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--yolo-batch", "4",
+                          "--dump-outputs", str(tmp_path / "out")], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "bf16" and line["unit"] == "images/sec"
+    assert abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) <= 1e-6 * line["value"]
+    assert set(line["workloads"]) == {"yolo"} and line["roofline"] is None and line["cpu_baseline"] is None and line["detail"] is None
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["yolo_grads.npy", "yolo_losses.npy", "yolo_params.npy"]
+    z = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert z["yolo_losses"].shape == (7,) and np.isfinite(z["yolo_losses"]).all() and z["yolo_losses"][0] > 0
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in z.values())
+    assert sum(v.nbytes for v in z.values()) <= 64 << 20 and np.abs(z["yolo_grads"]).max() > 0
 
 
 def test_rccl_allreduce_path_single_rank():

@@ -249,6 +249,25 @@ def test_bench_line_fits_the_drivers_capture():
     assert "workloads" not in out and out["roofline"] and out["cpu_baseline"] and len(json.dumps(out)) <= bench.MAX_LINE_BYTES
 
 
+def test_bench_dump_outputs_samples_large_outputs_the_same_way(tmp_path):
+    """bench.py --dump-outputs: small outputs keep their shape, a large one is a seeded sample of fixed positions, integer indices come out
+    float64 and everything else float32, and more than 64 MB in all is refused."""
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE * 3, dtype=torch.float32)
+    arrays = {"loss": torch.tensor([1.5, 2.5]), "big": big, "idx": torch.arange(5), "h": torch.ones(2, 3, dtype=torch.bfloat16)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in arrays}
+    assert a["loss"].dtype == np.float32 and a["loss"].tolist() == [1.5, 2.5]
+    assert a["idx"].dtype == np.float64 and a["h"].dtype == np.float32 and a["h"].shape == (2, 3)
+    assert a["big"].ndim == 1 and bench.DUMP_SAMPLE // 2 < a["big"].size <= bench.DUMP_SAMPLE
+    assert np.all(np.diff(a["big"]) > 0) and np.array_equal(a["big"], b["big"])       # sorted positions, the same in both runs
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), {f"t{i}": big for i in range(12)})
+
+
 _SHIM_PROBE = r"""
 import importlib.util, os, sys
 shim, ref = sys.argv[1], sys.argv[2]
