@@ -264,6 +264,27 @@ int mdcv_crop_resize_u8(const unsigned char* frames, int B, int C, int H, int W,
 int mdcv_synth_cone_batch(unsigned int seed, int step, int B, int T, int H, int W, int num_classes, float* images, float* targets, void* stream);
 int mdcv_synth_crop_batch(unsigned int seed, int step, int B, int size, float* images, float* heatmaps, float* points, void* stream);
 
+/* ---- real-image detector batches (csrc/imgload.hip; CVC-YOLOv3/utils/datasets.py:124-315 ImageLabelDataset.__getitem__, image half):
+ *      decoded uint8 RGB source windows -> Pillow's 8-bit convolution resize (horizontal pass into a uint8 scratch, then vertical), the
+ *      127 padding and patch crop around it, convert('L') when C == 1, hflip, and to_tensor's /255 into out [B,C,H,W] fp32; byte-exact.
+ *      The resize input is a VIRTUAL image: a 127 canvas holding the window's bytes, so padding in front of the filter (the pad-and-resize
+ *      path) reads 127 at the border taps.  One descriptor of MDCV_IMGLOAD_DESC ints per image (mdcv/data/images.py writes them):
+ *       [0] src_off   byte offset of the window in `src` (HWC, rows of win_w * 3 bytes)   [1] win_w  [2] win_h
+ *       [3] ksize_x   [4] ksize_y   [5] cx_off  [6] cy_off   offsets in `coefs` (ints) of the column / row tables; entry j of a table is
+ *                     ksize + 2 ints: first tap (window column / scratch row), tap count, ksize 22-bit fixed-point coefficients
+ *       [7] scr_w     resized columns computed (column table entries)   [8] scr_h  scratch rows: virtual rows [row0, row0 + scr_h)
+ *       [9] row0      virtual row of scratch row 0, relative to the window's first row   [10] ny  resized rows (row table entries)
+ *       [11] ox_off   [12] oy_off   output (x, y) + off = resized (column, row) index into the tables; x is read mirrored when flip
+ *       [13..16]      pad_x0, pad_x1, pad_y0, pad_y1: outside the resized image but inside this box (same coordinates) -> 127, else 0
+ *       [17] flip     [18], [19] must be 0
+ *      desc_host is validated (MDCV_EARG) and sizes nothing else; desc is its device copy, which the kernels read and check again (an
+ *      image whose device descriptor fails the checks is written as zeros).  Scratch: mdcv_imgload_workspace_bytes(B, max_scr_w, max_scr_h);
+ *      every descriptor needs scr_w <= max_scr_w, scr_h <= max_scr_h.  C in {1, 3}. */
+#define MDCV_IMGLOAD_DESC 20
+long long mdcv_imgload_workspace_bytes(int B, int max_scr_w, int max_scr_h);
+int mdcv_imgload_batch(const int* desc_host, const int* desc, int B, const int* coefs, long long n_coefs, const unsigned char* src,
+                       long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace, float* out, void* stream);
+
 /* ---- optimizer step over the flat fp32 parameter buffer (train.py:180-187,72 ; train_eval.py:263,72) */
 int mdcv_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr, float beta1,
                    float beta2, float eps, float weight_decay, float grad_scale, void* stream);

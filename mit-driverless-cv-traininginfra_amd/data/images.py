@@ -1,0 +1,562 @@
+"""Real-image detector batches: `ImageLabelBatches` stands where `DataLoader(ImageLabelDataset(...))` stands in CVC-YOLOv3/train.py:124-141.
+
+The host decodes (Pillow, on a thread pool) and crops each frame to the source window its output patch reads; everything from that
+uint8 window to the `[B,C,H,W]` fp32 batch runs in csrc/imgload.hip (two launches per batch).  What the reference's chain computes
+(CVC-YOLOv3/utils/datasets.py:124-315 with utils/utils.py's geometry and label helpers, torchvision 0.3's pad / resize / to_grayscale /
+hflip / to_tensor over Pillow) is reproduced exactly:
+
+* images: Pillow's 8-bit convolution resize (`Image.resize(size, filter)`, reducing_gap=None) -- LANCZOS for tile-and-scale (`ts`,
+  utils.py:321-326 `scale_image`), antialiased BILINEAR for pad-and-resize -- with coefficient tables computed here in float64 the way
+  Pillow's `precompute_coeffs` computes them (cached per (in, out, filter)); the 127 padding, the patch crop (`Image.crop` rounds the box
+  with `round`), `convert('L')`, `FLIP_LEFT_RIGHT` and `/255` in fp32 around it, all on the device.
+* labels: the reference's helpers restated in NumPy with torch's arithmetic (float32 tensors; a Python scalar meeting one is rounded to
+  float32 first; `filter_and_offset_labels` mixes 0-dim float32 tensors with Python doubles), computed on the host and shipped with the
+  pixels in the same pinned buffer and the same copy.
+* random draws: per sample from `random.Random(f"{seed}/{epoch}/{index}")`, in the reference's order: the patch, then the flip.
+
+Not supported (ValueError): the photometric / affine / imgaug augmentations (their semantics belong to torchvision 0.3 and imgaug).
+"""
+import csv
+import json
+import math
+import os
+import random
+import warnings
+from concurrent.futures import ThreadPoolExecutor
+from functools import lru_cache
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+PRECISION_BITS = 22                      # Pillow Resample.c: 32 - 8 - 2
+DESC = 20                                # MDCV_IMGLOAD_DESC
+LANCZOS, BILINEAR = "lanczos", "bilinear"
+UNSUPPORTED = ("augment_affine", "augment_hsv", "data_aug", "blur", "noise", "contrast", "sharpen", "salt")
+_F32 = np.float32
+
+
+# ---------------------------------------------------------------------------------------------------------------- Pillow's resampler
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x               # libm sin, as Pillow: a one-ulp difference can flip a fixed-point rounding
+
+
+def _lanczos(x):
+    if -3.0 <= x < 3.0:
+        return _sinc(x) * _sinc(x / 3)
+    return 0.0
+
+
+def _bilinear(x):
+    if x < 0.0:
+        x = -x
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+_FILTERS = {LANCZOS: (_lanczos, 3.0), BILINEAR: (_bilinear, 1.0)}
+
+
+@lru_cache(maxsize=512)
+def resample_coeffs(in_size, out_size, filt):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for a full-width box -> (ksize, first[out], count[out], kk[out, ksize] int32).
+
+    A same-size axis is a copy (Pillow skips that pass): one tap of weight 1 << 22."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f"resample: sizes must be positive, got {in_size} -> {out_size}")
+    if in_size == out_size:
+        r = np.arange(out_size, dtype=np.int32)
+        return 1, r, np.ones(out_size, np.int32), np.full((out_size, 1), 1 << PRECISION_BITS, np.int32)
+    fn, fsupport = _FILTERS[filt]
+    scale = filterscale = float(in_size) / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = fsupport * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    first = np.zeros(out_size, np.int32)
+    count = np.zeros(out_size, np.int32)
+    kk = np.zeros((out_size, ksize), np.int32)
+    ss = 1.0 / filterscale
+    one = float(1 << PRECISION_BITS)
+    for xx in range(out_size):
+        center = 0.0 + (xx + 0.5) * scale
+        xmin = int(center - support + 0.5)
+        if xmin < 0:
+            xmin = 0
+        xmax = int(center + support + 0.5)
+        if xmax > in_size:
+            xmax = in_size
+        xmax -= xmin
+        w = [fn((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x in range(xmax):
+            k = w[x] / ww if ww != 0.0 else w[x]
+            kk[xx, x] = int(-0.5 + k * one) if k < 0 else int(0.5 + k * one)
+        first[xx], count[xx] = xmin, xmax
+    return ksize, first, count, kk
+
+
+# ------------------------------------------------------------------------------------------------- frame layout (both modes)
+# The arithmetic below is what makes the labels exact, so its form is fixed: Python ints where the layout is whole pixels, int()
+# truncation toward zero of the letterbox border, ceil of half the missing width, and patch starts that stay unrounded floats.
+
+def letterbox(frame_w, frame_h, out_w, out_h):
+    """Pad-and-resize layout (CVC-YOLOv3/utils/utils.py calculate_padding) -> (border_x, border_y, label_scale).
+
+    The frame gets a 127 border on its shorter-than-needed axis so that it takes the output's aspect ratio, then the bordered frame is
+    resized to out_w x out_h.  A frame at least as tall as it is wide is bordered left and right; any other, top and bottom."""
+    if frame_h >= frame_w:
+        return int((frame_h * out_w / out_h - frame_w) / 2), 0, out_h / frame_h
+    return 0, int((frame_w * out_h / out_w - frame_h) / 2), out_w / frame_w
+
+
+def scaled_size(width, height, scale):
+    return int(width * scale), int(height * scale)          # scale_image: (int(W * s), int(H * s))
+
+
+def tile_grid(scaled_w, scaled_h, patch_w, patch_h):
+    """Tile-and-scale layout (utils.py pre_tile_padding / get_patch_spacings) of a scaled frame
+    -> (border_x, border_y, cols, rows, step_back_x, step_back_y).
+
+    An axis shorter than a patch is centred between 127 borders of ceil(missing / 2); the bordered axis is then covered by the fewest
+    patches that reach its end, and the surplus is shared evenly: patch k along an axis starts at k * (patch - step_back)."""
+    def axis(n, p):
+        border = math.ceil((p - n) / 2) if n < p else 0
+        full = n + 2 * border
+        count = math.ceil(full / p)
+        back = (count * p - full) / (count - 1) if count > 1 else 0
+        return border, count, back
+    bx, cols, sx = axis(scaled_w, patch_w)
+    by, rows, sy = axis(scaled_h, patch_h)
+    return bx, by, cols, rows, sx, sy
+
+
+def patch_box(grid, patch_w, patch_h, index):
+    """Unrounded (left, top, right, bottom) of patch `index` (row-major over the grid) in bordered-frame coordinates: the box that
+    utils.py get_patch crops (after Image.crop rounds it) and filters the labels against (as it is)."""
+    _, _, cols, _, sx, sy = grid
+    c, r = index % cols, index // cols
+    left = patch_w * c - sx * c
+    top = patch_h * r - sy * r
+    return left, top, left + patch_w, top + patch_h
+
+
+def n_patches(frame_w, frame_h, scale, width, height):
+    g = tile_grid(*scaled_size(frame_w, frame_h, scale), width, height)
+    return g[2] * g[3]
+
+
+# ------------------------------------------------------------------------------------------------------------- per-sample geometry
+class Geometry:
+    """Where one output image comes from: the frame window to upload, its kernel descriptor (offsets left 0) and tables, and the
+    quantities the label pipeline needs (paddings, the unrounded patch boundary, the pad-and-resize ratio)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _axis(in_size, out_size, filt, o2s, n_out, src_lo, src_hi):
+    """One axis of the resize: output index o reads resized index o + o2s (inside [0, out_size)); the resize input is a virtual
+    line of in_size samples of which [src_lo, src_hi) are frame samples and the rest the 127 canvas."""
+    ksize, first, count, kk = resample_coeffs(in_size, out_size, filt)
+    s0, s1 = max(0, o2s), min(out_size, o2s + n_out)
+    if s1 <= s0:
+        s0 = s1 = max(0, min(out_size, o2s))
+    f, c = first[s0:s1].astype(np.int64), count[s0:s1].astype(np.int64)
+    tmin, tmax = (int(f.min()), int((f + c).max())) if s1 > s0 else (0, 0)
+    w0, w1 = max(tmin, src_lo), min(tmax, src_hi)
+    if w1 <= w0:
+        w0 = w1 = tmin
+    return dict(ksize=ksize, s0=s0, n=s1 - s0, first=f, count=c, kk=kk[s0:s1], tmin=tmin, tmax=tmax, w0=w0, w1=w1,
+                src_lo=src_lo, off=o2s - s0)
+
+
+def sample_geometry(frame_w, frame_h, width, height, ts, scale=1.0, patch_index=0, flip=False):
+    frame_w, frame_h, width, height = int(frame_w), int(frame_h), int(width), int(height)
+    if ts:
+        sw, sh = scaled_size(frame_w, frame_h, scale)
+        if sw <= 0 or sh <= 0:
+            raise ValueError(f"scale {scale} shrinks a {frame_w}x{frame_h} frame to nothing")
+        grid = tile_grid(sw, sh, width, height)
+        hp, vp, n = grid[0], grid[1], grid[2] * grid[3]
+        if not 0 <= patch_index < n:
+            raise ValueError(f"patch index {patch_index} outside 0..{n - 1}")
+        boundary = patch_box(grid, width, height, patch_index)
+        x0, y0, x1, y1 = map(int, map(round, boundary))           # Image.crop
+        if x1 - x0 != width or y1 - y0 != height:
+            raise ValueError(f"patch box {boundary} rounds to {x1 - x0}x{y1 - y0}, not {width}x{height} (odd patch size with a .5 offset)")
+        ax = _axis(frame_w, sw, LANCZOS, x0 - hp, width, 0, frame_w)
+        ay = _axis(frame_h, sh, LANCZOS, y0 - vp, height, 0, frame_h)
+        pad_x, pad_y = (-hp, sw + hp), (-vp, sh + vp)
+        g = dict(hp=hp, vp=vp, boundary=boundary, n_patches=n, ratio=None, pad_w=None, pad_h=None)
+    else:
+        pad_w, pad_h, ratio = letterbox(frame_w, frame_h, width, height)
+        pw_, ph_ = frame_w + 2 * pad_w, frame_h + 2 * pad_h
+        if pw_ <= 0 or ph_ <= 0:
+            raise ValueError(f"padding {pad_w},{pad_h} leaves nothing of a {frame_w}x{frame_h} frame")
+        ax = _axis(pw_, width, BILINEAR, 0, width, pad_w, pad_w + frame_w)
+        ay = _axis(ph_, height, BILINEAR, 0, height, pad_h, pad_h + frame_h)
+        pad_x, pad_y = (0, width), (0, height)
+        g = dict(hp=None, vp=None, boundary=None, n_patches=1, ratio=ratio, pad_w=pad_w, pad_h=pad_h)
+    win = (ax["w0"] - ax["src_lo"], ay["w0"] - ay["src_lo"], ax["w1"] - ax["w0"], ay["w1"] - ay["w0"])   # frame x, y, w, h
+    col = np.empty((ax["n"], ax["ksize"] + 2), np.int32)
+    col[:, 0], col[:, 1], col[:, 2:] = ax["first"] - ax["w0"], ax["count"], ax["kk"]
+    row = np.empty((ay["n"], ay["ksize"] + 2), np.int32)
+    row[:, 0], row[:, 1], row[:, 2:] = ay["first"] - ay["tmin"], ay["count"], ay["kk"]
+    desc = [0, win[2], win[3], ax["ksize"], ay["ksize"], 0, 0, ax["n"], ay["tmax"] - ay["tmin"], ay["tmin"] - ay["w0"], ay["n"],
+            ax["off"], ay["off"], pad_x[0] - ax["s0"], pad_x[1] - ax["s0"], pad_y[0] - ay["s0"], pad_y[1] - ay["s0"], int(bool(flip)), 0, 0]
+    return Geometry(ts=bool(ts), frame=(frame_w, frame_h), width=width, height=height, scale=scale, patch_index=patch_index,
+                    flip=bool(flip), window=win, desc=desc, col=col, row=row, **g)
+
+
+def crop_window(frame, geom):
+    """The bytes the kernel reads: the frame (H, W, 3 uint8) cropped to geom.window, contiguous."""
+    x, y, w, h = geom.window
+    if frame.shape[1] != geom.frame[0] or frame.shape[0] != geom.frame[1]:
+        raise ValueError(f"frame is {frame.shape[1]}x{frame.shape[0]}, the geometry was planned for {geom.frame[0]}x{geom.frame[1]}")
+    return np.ascontiguousarray(frame[y:y + h, x:x + w, :3], dtype=np.uint8)
+
+
+# ----------------------------------------------------------------------------------------------------------- labels (host, exact)
+def _t(a, b):            # a 0-dim float32 tensor meeting a Python number: the number is rounded to float32 first
+    if isinstance(a, np.float32) or isinstance(b, np.float32):
+        return _F32(a), _F32(b)
+    return a, b
+
+
+def _sub(a, b):
+    a, b = _t(a, b)
+    return a - b
+
+
+def _min(a, b):          # Python's min / max over (tensor, float): compare in float32, keep the first on ties
+    x, y = _t(a, b)
+    return b if y < x else a
+
+
+def _max(a, b):
+    x, y = _t(a, b)
+    return b if y > x else a
+
+
+def filter_and_offset_labels(labels, boundary):
+    """utils.py filter_and_offset_labels with its mixed float32 / double arithmetic; labels float32 [n,5]"""
+    left, top, right, bottom = boundary
+    out = []
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for c, x0, y0, x1, y1 in labels:
+            box_area = _F32(_F32(x1 - x0) * _F32(y1 - y0))
+            dx = _sub(_min(x1, right), _max(x0, left))
+            dy = _sub(_min(y1, bottom), _max(y0, top))
+            if dx >= 0 and dy >= 0:
+                p = _t(dx, dy)
+                overlap = float(p[0] * p[1])
+            else:
+                overlap = 0
+            if _F32(overlap) / box_area > _F32(0.5) or overlap > 1000:
+                nx0, ny0 = _max(x0, left), _max(y0, top)
+                nx1, ny1 = _min(x1, right), _min(y1, bottom)
+                out.append([c, _sub(nx0, left), _sub(ny0, top), _sub(nx1, left), _sub(ny1, top)])
+    if out:
+        return np.array([[_F32(v) for v in r] for r in out], dtype=_F32)
+    return np.zeros((len(labels), 5), _F32)
+
+
+def sample_labels(boxes, geom, num_targets):
+    """ImageLabelDataset.__getitem__'s label half for raw CSV boxes [n,4] (x, y, h, w) -> float32 [num_targets, 5] (cls, cx, cy, w, h)."""
+    boxes = np.asarray(boxes, _F32).reshape(-1, 4)
+    out = np.zeros((num_targets, 5), _F32)
+    if len(boxes) == 0:
+        return out
+    l = np.zeros((len(boxes), 5), _F32)                      # add_class_dimension_to_labels, xyhw2xyxy_corner (class stays 0)
+    l[:, 1], l[:, 2] = boxes[:, 0], boxes[:, 1]
+    l[:, 3], l[:, 4] = boxes[:, 0] + boxes[:, 3], boxes[:, 1] + boxes[:, 2]
+    if geom.ts:
+        l[:, 1:5] = _F32(geom.scale) * l[:, 1:5]              # scale_labels
+        l[:, 1:5] = l[:, 1:5] + np.array([geom.hp, geom.vp, geom.hp, geom.vp], _F32)   # add_padding_on_each_side
+        l = filter_and_offset_labels(l, geom.boundary)
+    else:
+        l[:, 1:5] = l[:, 1:5] + np.array([geom.pad_w, geom.pad_h, geom.pad_w, geom.pad_h], _F32)
+        l[:, 1:5] = _F32(geom.ratio) * l[:, 1:5]
+    if geom.flip:
+        l[:, 1] = _F32(geom.width) - l[:, 1]
+        l[:, 3] = _F32(geom.width) - l[:, 3]
+    x = l[:, 1:5].copy()                                       # xyxy2xywh
+    l[:, 1], l[:, 2] = (x[:, 0] + x[:, 2]) / _F32(2), (x[:, 1] + x[:, 3]) / _F32(2)
+    l[:, 3], l[:, 4] = np.abs(x[:, 2] - x[:, 0]), np.abs(x[:, 3] - x[:, 1])
+    l[:, (1, 3)] /= _F32(geom.width)
+    l[:, (2, 4)] /= _F32(geom.height)
+    if len(l) > num_targets:
+        raise ValueError(f"{len(l)} labels for {num_targets} target rows")
+    out[:len(l)] = l
+    if (out < 0).any():
+        raise ValueError("labels have negative values")
+    return out
+
+
+def read_label_csv(path, dataset_path):
+    """ImageLabelDataset's CSV contract -> [(file, width, height, scale, boxes float32 [n,4])]: rows from the third line on, boxes are the
+    JSON cells from column 5 on, rows with a negative coordinate are skipped with a warning."""
+    rows = []
+    with open(path) as f:
+        for i, row in enumerate(csv.reader(f)):
+            if i < 2:
+                continue
+            boxes = [json.loads(cell) for cell in row[5:] if cell]
+            boxes = np.array(boxes, _F32).reshape(-1, 4) if boxes else np.zeros((0, 4), _F32)
+            if (boxes < 0).any():
+                warnings.warn(f"Image {os.path.join(dataset_path, row[0])} at line {i + 1} has negative bounding box coordinates; skipping")
+                continue
+            rows.append((os.path.join(dataset_path, row[0]), int(row[2]), int(row[3]), float(row[4]), boxes))
+    return rows
+
+
+# -------------------------------------------------------------------------------------------------------------------- the batch
+def _align(n, a=16):
+    return (n + a - 1) // a * a
+
+
+class _Packed:
+    pass
+
+
+def pack_layout(geoms, windows_nbytes, num_targets):
+    """Byte layout of one batch's staging buffer: [descriptors][labels][coefficient tables][pixels]."""
+    p = _Packed()
+    B = len(geoms)
+    p.B, p.T = B, num_targets
+    p.desc_off, p.lab_off = 0, _align(B * DESC * 4)
+    p.coef_off = _align(p.lab_off + B * num_targets * 5 * 4)
+    n_coef = sum(g.col.size + g.row.size for g in geoms)
+    p.n_coefs = max(n_coef, 1)
+    p.pix_off = _align(p.coef_off + p.n_coefs * 4)
+    p.src_bytes = sum(windows_nbytes)
+    p.nbytes = _align(p.pix_off + p.src_bytes)
+    p.max_scr_w = max(g.desc[7] for g in geoms)
+    p.max_scr_h = max(g.desc[8] for g in geoms)
+    return p
+
+
+def pack_batch(buf, p, geoms, windows, labels=None):
+    """Fill a uint8 numpy buffer of at least p.nbytes bytes (the pinned staging) with the batch."""
+    desc = buf[p.desc_off:p.desc_off + p.B * DESC * 4].view(np.int32).reshape(p.B, DESC)
+    coefs = buf[p.coef_off:p.coef_off + p.n_coefs * 4].view(np.int32)
+    c, s = 0, 0
+    for b, (g, w) in enumerate(zip(geoms, windows)):
+        d = list(g.desc)
+        d[0] = s
+        d[5] = c
+        coefs[c:c + g.col.size] = g.col.reshape(-1)
+        c += g.col.size
+        d[6] = c
+        coefs[c:c + g.row.size] = g.row.reshape(-1)
+        c += g.row.size
+        desc[b] = d
+        buf[p.pix_off + s:p.pix_off + s + w.nbytes] = w.reshape(-1)
+        s += w.nbytes
+    if p.T and labels is not None:
+        buf[p.lab_off:p.lab_off + p.B * p.T * 20].view(np.float32)[:] = np.asarray(labels, np.float32).reshape(-1)
+
+
+def launch_batch(dev_buf, host_buf, p, channels, height, width, stream):
+    """Enqueue the kernel pair on `stream` for a staged batch already copied to `dev_buf` (device uint8) -> imgs [B,C,H,W]."""
+    L = _lib.lib()
+    dev = dev_buf.device
+    imgs = torch.empty(p.B, channels, height, width, dtype=torch.float32, device=dev)
+    wsb = L.imgload_workspace_bytes(p.B, p.max_scr_w, p.max_scr_h)
+    ws = torch.empty(max(int(wsb), 1), dtype=torch.uint8, device=dev)
+    base = dev_buf.data_ptr()
+    L.check(L.imgload_batch(host_buf.ctypes.data + p.desc_off, base + p.desc_off, p.B, base + p.coef_off, p.n_coefs, base + p.pix_off,
+                            p.src_bytes, p.max_scr_w, p.max_scr_h, channels, height, width, ws.data_ptr(), imgs.data_ptr(),
+                            stream.cuda_stream), "imgload_batch")
+    return imgs
+
+
+def transform_batch(frames, geoms, bw=False, device=None):
+    """Synchronous convenience (tests, probes): decoded frames [(H, W, 3) uint8] + their geometries -> imgs [B,C,H,W] fp32 on the device."""
+    _lib.require_gpu()
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    windows = [crop_window(f, g) for f, g in zip(frames, geoms)]
+    p = pack_layout(geoms, [w.nbytes for w in windows], 0)
+    host = np.zeros(p.nbytes, np.uint8)
+    pack_batch(host, p, geoms, windows)
+    with torch.cuda.device(device):
+        dev = torch.from_numpy(host).to(device)
+        return launch_batch(dev, host, p, 1 if bw else 3, geoms[0].height, geoms[0].width, torch.cuda.current_stream(device))
+
+
+def _default_decode(path):
+    from PIL import Image
+    return Image.open(path).convert("RGB")
+
+
+class _Slot:
+    def __init__(self):
+        self.pinned, self.event = None, None
+
+
+class ImageLabelBatches:
+    """Iterable of `(uris, imgs [B,C,H,W] fp32, targets [B,T,5] fp32)` on the device, C = 1 when `bw` else 3: the batches that
+    `DataLoader(ImageLabelDataset(path, dataset_path, width, height, ..., num_images, bw, lr_flip, ts), batch_size, shuffle)` yields.
+
+    `decode(path)` -> a PIL image or an (H, W, 3) uint8 array (default: `PIL.Image.open(path).convert('RGB')`), run on `num_workers`
+    threads.  `draws(epoch, index)` -> (patch_index, flip) overrides the random draws (tests).  `subset_seed` seeds the
+    `random.sample` of `num_images`; its default 0 is the `random.seed(0)` that CVC-YOLOv3/train.py:40 runs before it builds its
+    loaders, so the training loader's subset is the one train.py draws.  `debug_mode` forces patch 0 as the reference does (the patch
+    draw still happens first, so the flip draw is unchanged).  With `prefetch`, batch i+1 is decoded and
+    staged while batch i is consumed; its copy runs on a side stream that the consumer's stream waits for when the batch is handed over.
+    """
+
+    def __init__(self, path, dataset_path, width, height, num_images=-1, bw=False, lr_flip=False, ts=True, batch_size=1, shuffle=True,
+                 num_workers=None, seed=0, device=None, decode=None, ud_flip=False, subset_seed=0, draws=None, prefetch=True, debug_mode=False,
+                 **options):
+        bad = [k for k in UNSUPPORTED if options.pop(k, False)]
+        if bad:
+            raise ValueError(f"ImageLabelBatches does not implement {', '.join(bad)} (torchvision 0.3 / imgaug augmentations); "
+                             "set them False")
+        for k in ("vis_batch", "upload_dataset", "n_cpu"):
+            options.pop(k, None)
+        if options:
+            raise TypeError(f"ImageLabelBatches: unknown arguments {sorted(options)}")
+        self.width, self.height, self.bw, self.lr_flip, self.ts = int(width), int(height), bool(bw), bool(lr_flip), bool(ts)
+        self.ud_flip = ud_flip                                   # accepted and ignored, as in the reference
+        self.debug_mode = bool(debug_mode)
+        self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
+        self.num_workers = int(num_workers) if num_workers is not None else max(1, min(16, os.cpu_count() or 1))
+        self.decode, self.draws, self.prefetch = decode or _default_decode, draws, bool(prefetch)
+        self._device = device
+        self.img_files, self.labels, self.scales, self.sizes = [], [], [], []
+        for file, w, h, scale, boxes in read_label_csv(path, dataset_path):
+            n = n_patches(w, h, scale, self.width, self.height) if self.ts else 1
+            self.img_files += [file] * n
+            self.labels += [boxes] * n
+            self.scales += [scale] * n
+            self.sizes += [(w, h)] * n
+        if num_images >= 0:
+            idx = random.Random(subset_seed).sample(range(len(self.img_files)), k=num_images)
+            if len(idx) > 1:                                     # the reference keeps everything for k <= 1
+                for name in ("img_files", "labels", "scales", "sizes"):
+                    v = getattr(self, name)
+                    setattr(self, name, [v[i] for i in idx])
+        self.num_targets_per_image = max((len(l) for l in self.labels), default=0)
+        self.dataset = range(len(self.img_files))               # len(loader.dataset), as train.py prints it
+        self.epoch = 0
+        self._pool = None
+        self._slots = [_Slot() for _ in range(3)]
+
+    def __len__(self):
+        return (len(self.img_files) + self.batch_size - 1) // self.batch_size
+
+    @property
+    def channels(self):
+        return 1 if self.bw else 3
+
+    def order(self, epoch):
+        idx = list(range(len(self.img_files)))
+        if self.shuffle:
+            random.Random(f"{self.seed}/{epoch}/order").shuffle(idx)
+        return idx
+
+    def plan(self, index, epoch=0, frame_size=None):
+        """Host-only: the draws, geometry and labels of sample `index` in `epoch` (frame_size: the decoded (W, H); default the CSV's)."""
+        w, h = frame_size if frame_size is not None else self.sizes[index]
+        rng = random.Random(f"{self.seed}/{epoch}/{index}")
+        patch = rng.randint(0, n_patches(w, h, self.scales[index], self.width, self.height) - 1) if self.ts else 0
+        if self.debug_mode:
+            patch = 0
+        flip = bool(self.lr_flip and len(self.labels[index]) > 0 and rng.random() > 0.5)
+        if self.draws is not None:
+            patch, flip = self.draws(epoch, index)
+            flip = bool(flip) and len(self.labels[index]) > 0        # raw-empty samples return before the flip
+        g = sample_geometry(w, h, self.width, self.height, self.ts, self.scales[index] if self.ts else 1.0, patch, flip)
+        g.index, g.uri = index, self.img_files[index]
+        g.labels = sample_labels(self.labels[index], g, self.num_targets_per_image)
+        return g
+
+    # -- host half: decode, plan, crop, stage
+    def _sample(self, epoch, index):
+        img = self.decode(self.img_files[index])
+        frame = img if isinstance(img, np.ndarray) else np.asarray(img, dtype=np.uint8)
+        if frame.ndim != 3 or frame.shape[2] < 3 or frame.dtype != np.uint8:
+            raise ValueError(f"{self.img_files[index]}: decode must give an (H, W, 3) uint8 RGB frame, got {frame.shape} {frame.dtype}")
+        g = self.plan(index, epoch, (frame.shape[1], frame.shape[0]))
+        return g, crop_window(frame, g)
+
+    def _stage(self, epoch, bi, slot):
+        order = self._orders[epoch]
+        idx = order[bi * self.batch_size:(bi + 1) * self.batch_size]
+        if self._pool is not None:
+            got = list(self._pool.map(lambda i: self._sample(epoch, i), idx))
+        else:
+            got = [self._sample(epoch, i) for i in idx]
+        geoms, windows = [g for g, _ in got], [w for _, w in got]
+        p = pack_layout(geoms, [w.nbytes for w in windows], self.num_targets_per_image)
+        if slot.event is not None:
+            slot.event.synchronize()                             # the previous copy out of this buffer has completed
+        if slot.pinned is None or slot.pinned.numel() < p.nbytes:
+            slot.pinned = torch.empty(_align(p.nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        host = slot.pinned.numpy()
+        pack_batch(host, p, geoms, windows, [g.labels for g in geoms])
+        return [g.uri for g in geoms], p, slot
+
+    # -- device half: one H2D copy and the kernel pair on the side stream
+    def _enqueue(self, staged):
+        uris, p, slot = staged
+        dev = self.device
+        with torch.cuda.device(dev), torch.cuda.stream(self._stream):
+            dbuf = torch.empty(p.nbytes, dtype=torch.uint8, device=dev)
+            dbuf.copy_(slot.pinned[:p.nbytes], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+            slot.event = ev
+            imgs = launch_batch(dbuf, slot.pinned.numpy(), p, self.channels, self.height, self.width, self._stream)
+            tg = dbuf[p.lab_off:p.lab_off + p.B * p.T * 20].view(torch.float32).view(p.B, p.T, 5).clone()
+            ready = torch.cuda.Event()
+            ready.record(self._stream)
+        return uris, imgs, tg, ready
+
+    @property
+    def device(self):
+        if self._device is None:
+            return torch.device("cuda", torch.cuda.current_device())
+        return torch.device(self._device)
+
+    def __iter__(self):
+        _lib.require_gpu()
+        epoch = self.epoch
+        self.epoch += 1
+        self._orders = {epoch: self.order(epoch)}
+        dev = self.device
+        self._stream = torch.cuda.Stream(dev)
+        nb = len(self)
+        if self.num_workers > 1 and self._pool is None:
+            self._pool = ThreadPoolExecutor(self.num_workers, thread_name_prefix="mdcv-decode")
+        stager = ThreadPoolExecutor(1, thread_name_prefix="mdcv-stage") if self.prefetch else None
+        try:
+            pending = {}
+            depth = 2 if self.prefetch else 0
+            for bi in range(nb):
+                for j in range(bi, min(nb, bi + depth + 1)):
+                    if j not in pending and self.prefetch:
+                        pending[j] = stager.submit(self._stage, epoch, j, self._slots[j % 3])
+                staged = pending.pop(bi).result() if self.prefetch else self._stage(epoch, bi, self._slots[bi % 3])
+                uris, imgs, tg, ready = self._enqueue(staged)
+                cons = torch.cuda.current_stream(dev)
+                cons.wait_event(ready)
+                imgs.record_stream(cons)
+                tg.record_stream(cons)
+                yield uris, imgs, tg
+        finally:
+            if stager is not None:
+                stager.shutdown(wait=True, cancel_futures=True)
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None

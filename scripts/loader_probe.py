@@ -1,0 +1,176 @@
+"""Rates of the real-image loader (mdcv.data.ImageLabelBatches, csrc/imgload.hip) on one GPU.
+
+(a) the device transform alone: ms per B=32 batch of 416x416 outputs from pre-decoded, pre-staged 1920x1080-class frames
+    (LANCZOS tile-and-scale at scale 0.5 / 1.0 / 1.5; BILINEAR pad-and-resize of a frame of 1920s x 1080s for the same s)
+(b) the whole loader with decode, img/s on 1 / 8 / 16 decode threads, PNG and JPEG files written to a temporary directory
+(c) ms per YOLOv3 416x416 B=32 bf16 train step fed by the loader against the same step fed by SyntheticCones
+
+Device events after a warm-up, profiler off.  usage: loader_probe.py [files per format (default 32)]"""
+import contextlib
+import io
+import os
+import random
+import sys
+import tempfile
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+from mdcv.data import images as I  # noqa: E402
+from mdcv.data.synth import SyntheticCones  # noqa: E402
+
+B, S = 32, 416
+NFILES = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+
+
+def frame(seed, w=1920, h=1080):
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:h, 0:w]
+    img = np.stack([x * 255 // w, y * 255 // h, (x + y) % 256], -1).astype(np.int16)
+    img += rng.integers(-12, 13, img.shape, dtype=np.int16)
+    return np.clip(img, 0, 255).astype(np.uint8)
+
+
+def ev_ms(fn, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    torch.cuda.synchronize()
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def part_a(frames):
+    print("(a) device transform alone, B=32 outputs of 416x416 RGB (ms per batch, kernel pair only; staged bytes per batch)")
+    rng = random.Random(0)
+    for filt in ("lanczos", "bilinear"):
+        for s in (0.5, 1.0, 1.5):
+            geoms, wins = [], []
+            for b in range(B):
+                f = frames[b % len(frames)]
+                if filt == "lanczos":
+                    n = I.n_patches(f.shape[1], f.shape[0], s, S, S)
+                    g = I.sample_geometry(f.shape[1], f.shape[0], S, S, True, s, rng.randrange(n), b % 2)
+                else:
+                    w, h = int(1920 * s), int(1080 * s)
+                    f = np.ascontiguousarray(np.resize(f, (h, w, 3)))
+                    g = I.sample_geometry(w, h, S, S, False, 1.0, 0, b % 2)
+                geoms.append(g)
+                wins.append(I.crop_window(f, g))
+            p = I.pack_layout(geoms, [w.nbytes for w in wins], 0)
+            host = np.zeros(p.nbytes, np.uint8)
+            I.pack_batch(host, p, geoms, wins)
+            dev = torch.from_numpy(host).cuda()
+            st = torch.cuda.current_stream()
+            ms = ev_ms(lambda: I.launch_batch(dev, host, p, 3, S, S, st), 50)
+            print(f"    {filt:8s} scale {s:3.1f}: {ms:7.3f} ms/batch  ({1e3 * B / ms:8.0f} img/s)  staged {p.nbytes / 2**20:6.2f} MiB "
+                  f"(ksize {geoms[0].desc[3]}, scratch {p.max_scr_w}x{p.max_scr_h})")
+
+
+def write_dataset(tmp, frames, fmt):
+    from PIL import Image
+    rng = random.Random(1)
+    rows = ["Name,URL,Width,Height,Scale,X0,Y0,H0,W0", "header"]
+
+    def save(i):
+        Image.fromarray(frames[i % len(frames)]).save(os.path.join(tmp, f"{i}.{fmt}"), quality=90) if fmt == "jpg" else \
+            Image.fromarray(frames[i % len(frames)]).save(os.path.join(tmp, f"{i}.{fmt}"), compress_level=1)
+    with ThreadPoolExecutor(16) as ex:
+        list(ex.map(save, range(NFILES)))
+    for i in range(NFILES):
+        boxes = []
+        for _ in range(rng.randint(1, 8)):
+            w, h = rng.randint(10, 60), rng.randint(15, 90)
+            boxes.append(f'"[{rng.randint(0, 1920 - w)}, {rng.randint(0, 1080 - h)}, {h}, {w}]"')
+        rows.append(",".join([f"{i}.{fmt}", "", "1920", "1080", "1.0"] + boxes))
+    path = os.path.join(tmp, f"train_{fmt}.csv")
+    with open(path, "w") as f:
+        f.write("\n".join(rows) + "\n")
+    return path
+
+
+def part_b(tmp, csvs):
+    print("(b) whole loader with decode, 416x416 tile-and-scale at scale 1.0, B=32 (img/s; decode alone on the same threads)")
+    from PIL import Image
+    for fmt, path in csvs.items():
+        files = [os.path.join(tmp, f"{i}.{fmt}") for i in range(NFILES)]
+        for t in (1, 8, 16):
+            frames_timed = 5 * B                       # as many frames as the loader run below decodes in its timed batches
+            with ThreadPoolExecutor(t) as ex:
+                list(ex.map(lambda p: np.asarray(Image.open(p).convert("RGB")), files[:B]))
+                t0 = time.perf_counter()
+                list(ex.map(lambda i: np.asarray(Image.open(files[i % NFILES]).convert("RGB")), range(frames_timed)))
+                dec = frames_timed / (time.perf_counter() - t0)
+            ld = I.ImageLabelBatches(path, tmp, S, S, ts=True, lr_flip=True, batch_size=B, num_workers=t)
+            it = iter(ld)
+            next(it)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = 0
+            for k, (_, imgs, tg) in enumerate(it):
+                n += imgs.shape[0]
+                if k == 4:
+                    break
+            torch.cuda.synchronize()
+            rate = n / (time.perf_counter() - t0)
+            ld.close()
+            print(f"    {fmt:4s} {t:2d} threads: loader {rate:7.0f} img/s   decode alone {dec:7.0f} frames/s")
+
+
+def part_c(tmp, csv_path, steps=10):
+    print(f"(c) YOLOv3 416x416 B=32 bf16 train step (ms/step over {steps} steps after 3 warm-up steps)")
+    from mdcv.optim import FusedAdam
+    from mdcv.yolo.models import Darknet
+    d = tempfile.mkdtemp()
+    cfg = bench.write_yolo_cfg(d, classes=1)
+    cwd = os.getcwd()
+    os.chdir(d)
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        net = Darknet(cfg, 2.0, 1.6, 25.0, 0.1, True, precision="bf16").cuda().train()
+    os.chdir(cwd)
+    opt = FusedAdam(net, lr=1e-4)
+
+    def run(data):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for i, (_, x, tg) in enumerate(data):
+            if i == 3:
+                s.record()
+            opt.zero_grad()
+            out = net(x, tg)
+            out[0].sum().backward()
+            opt.step()
+            if i == 3 + steps - 1:
+                e.record()
+                break
+        e.synchronize()
+        return s.elapsed_time(e) / steps
+
+    syn = run(SyntheticCones(B, S, S, 16, 1, batches=steps + 4, seed=3))
+    for t in (16, 8):
+        ld = I.ImageLabelBatches(csv_path, tmp, S, S, ts=True, lr_flip=False, batch_size=B, num_workers=t)
+        real = run(ld)
+        ld.close()
+        print(f"    SyntheticCones: {syn:7.2f} ms/step   ImageLabelBatches (JPEG, {t:2d} threads): {real:7.2f} ms/step")
+
+
+def main():
+    torch.cuda.set_device(0)
+    frames = [frame(i) for i in range(8)]
+    part_a(frames)
+    with tempfile.TemporaryDirectory() as tmp:
+        csvs = {fmt: write_dataset(tmp, frames, fmt) for fmt in ("png", "jpg")}
+        part_b(tmp, csvs)
+        part_c(tmp, csvs["jpg"])
+
+
+if __name__ == "__main__":
+    main()
