@@ -285,6 +285,27 @@ long long mdcv_imgload_workspace_bytes(int B, int max_scr_w, int max_scr_h);
 int mdcv_imgload_batch(const int* desc_host, const int* desc, int B, const int* coefs, long long n_coefs, const unsigned char* src,
                        long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace, float* out, void* stream);
 
+/* ---- the same batches with the reference's training augmentation (csrc/imgaug.hip; datasets.py:226-242 over torchvision 0.3's ColorJitter
+ *      and F.affine, which are Pillow's ImageEnhance blends, convert('HSV') / convert('RGB') and Image.transform(AFFINE, BILINEAR, fill 127)):
+ *      patch -> jitter -> affine -> convert('L') when C == 1 -> hflip -> /255 into out [B,C,H,W] fp32; byte-exact against Pillow 12.2.
+ *      desc_host / desc / coefs / src / workspace are mdcv_imgload_batch's.  One more descriptor of MDCV_IMGAUG_DESC ints per image:
+ *       [0..11]   six doubles (low word first): Image.transform's AFFINE data, output pixel centre -> input position; read when [21] is 1
+ *       [12] jitter   0 / 1
+ *       [13..16]  the order of the four ops, a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue
+ *       [17..19]  float32 bits of the brightness, contrast and saturation factors (Image.blend's alpha), each in [0, 16]
+ *       [20] hue      the uint8 added to the H channel, 0..255
+ *       [21] affine   0 / 1        [22], [23] must be 0
+ *      An image with [12] == [21] == 0 comes out as mdcv_imgload_batch writes it.  aug_host is validated (MDCV_EARG); aug is its device
+ *      copy, checked again by the kernels (an image whose device descriptors fail is written as zeros).  No entry of this descriptor
+ *      indexes memory: every tap is clamped to the H x W patch.  aug_workspace: mdcv_imgaug_workspace_bytes(B, H, W) bytes (the uint8
+ *      RGBX patches and one luma sum per image, which bounds H * W by 4096 * 4096).  Launches: horizontal pass, uint8 patch, the luma
+ *      sums (only when some image's jitter is on), apply. */
+#define MDCV_IMGAUG_DESC 24
+long long mdcv_imgaug_workspace_bytes(int B, int H, int W);
+int mdcv_imgload_aug_batch(const int* desc_host, const int* desc, const int* aug_host, const int* aug, int B, const int* coefs, long long n_coefs,
+                           const unsigned char* src, long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace,
+                           void* aug_workspace, float* out, void* stream);
+
 /* ---- optimizer step over the flat fp32 parameter buffer (train.py:180-187,72 ; train_eval.py:263,72) */
 int mdcv_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr, float beta1,
                    float beta2, float eps, float weight_decay, float grad_scale, void* stream);

@@ -1,7 +1,8 @@
 """Real-image detector batches: `ImageLabelBatches` stands where `DataLoader(ImageLabelDataset(...))` stands in CVC-YOLOv3/train.py:124-141.
 
 The host decodes (Pillow, on a thread pool) and crops each frame to the source window its output patch reads; everything from that
-uint8 window to the `[B,C,H,W]` fp32 batch runs in csrc/imgload.hip (two launches per batch).  What the reference's chain computes
+uint8 window to the `[B,C,H,W]` fp32 batch runs in csrc/imgload.hip (two launches per batch) or, for a batch with an augmented sample,
+csrc/imgaug.hip (three or four).  What the reference's chain computes
 (CVC-YOLOv3/utils/datasets.py:124-315 with utils/utils.py's geometry and label helpers, torchvision 0.3's pad / resize / to_grayscale /
 hflip / to_tensor over Pillow) is reproduced exactly:
 
@@ -12,9 +13,22 @@ hflip / to_tensor over Pillow) is reproduced exactly:
 * labels: the reference's helpers restated in NumPy with torch's arithmetic (float32 tensors; a Python scalar meeting one is rounded to
   float32 first; `filter_and_offset_labels` mixes 0-dim float32 tensors with Python doubles), computed on the host and shipped with the
   pixels in the same pinned buffer and the same copy.
-* random draws: per sample from `random.Random(f"{seed}/{epoch}/{index}")`, in the reference's order: the patch, then the flip.
+* augmentation (`augment_hsv`, `augment_affine`, `data_aug`; datasets.py:226-242): torchvision 0.3's `ColorJitter(brightness=0.25,
+  contrast=0.25, saturation=0.25, hue=0.04)` with probability 0.5, then `F.affine(angle, translate, scale, shear, BILINEAR, fillcolor=127)`
+  of every sample that has boxes, between the patch crop and to_grayscale.  Both are glue over Pillow and are reproduced byte for byte:
+  `ImageEnhance.Brightness / Contrast / Color` are `Image.blend` against 0 / the mean luma / the pixel's luma, `adjust_hue` is
+  `convert('HSV')`, a wrapping uint8 shift of H and `convert('RGB')`, `F.affine` is `Image.transform(AFFINE, BILINEAR)` with the inverse
+  matrix computed here in float64 (libm).  The hue shift is `int(hue_factor * 255)` truncated toward zero, modulo 256: what
+  `np.uint8(float)` gave on x86-64 with the NumPy of torchvision 0.3's time (NumPy 2 raises OverflowError for the negative ones).
+  The boxes follow `affine_labels` in float32 torch CPU arithmetic, in the reference's sequence of operations.
+* random draws: per sample from `random.Random(f"{seed}/{epoch}/{index}")`, in the reference's order: the patch; with `augment_hsv or
+  data_aug` the jitter gate `random()`, and when it is `> 0.5` the brightness, contrast, saturation (`uniform(0.75, 1.25)`) and hue
+  (`uniform(-0.04, 0.04)`) factors and the `shuffle` of the four ops; with `augment_affine or data_aug` the gate `random()` (`> 0`), angle
+  `uniform(-10, 10)`, tx, ty `uniform(-40, 40)`, scale `uniform(0.9, 1.1)`, shear `uniform(-3, 3)`; then the flip.  A sample without boxes
+  returns before all of this, as in the reference.  With the three options off no extra draw happens.
 
-Not supported (ValueError): the photometric / affine / imgaug augmentations (their semantics belong to torchvision 0.3 and imgaug).
+Not supported (ValueError): the imgaug augmentations `blur`, `noise`, `contrast`, `sharpen`, `salt` (imgaug draws its noise from NumPy's
+generator; nothing available pins them).
 """
 import csv
 import json
@@ -32,8 +46,10 @@ from .. import _lib
 
 PRECISION_BITS = 22                      # Pillow Resample.c: 32 - 8 - 2
 DESC = 20                                # MDCV_IMGLOAD_DESC
+AUG_DESC = 24                            # MDCV_IMGAUG_DESC
 LANCZOS, BILINEAR = "lanczos", "bilinear"
-UNSUPPORTED = ("augment_affine", "augment_hsv", "data_aug", "blur", "noise", "contrast", "sharpen", "salt")
+UNSUPPORTED = ("blur", "noise", "contrast", "sharpen", "salt")
+BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3        # ColorJitter.get_params appends its four ops in this order
 _F32 = np.float32
 
 
@@ -223,6 +239,131 @@ def crop_window(frame, geom):
     return np.ascontiguousarray(frame[y:y + h, x:x + w, :3], dtype=np.uint8)
 
 
+# ------------------------------------------------------------------------------------------------ augmentation (draws, matrix, boxes)
+class Augmentation:
+    """One sample's ColorJitter / affine parameters.  jitter: None or (order, (brightness, contrast, saturation), hue) with `order` the
+    shuffled permutation of (BRIGHTNESS, CONTRAST, SATURATION, HUE); affine: None or (angle, (tx, ty), scale, shear).  `matrix` (the six
+    doubles Image.transform gets) is filled in by `plan()`; `hue_shift` is the uint8 added to H.  The contrast op's grey level is the
+    one value only the device knows: the mean luma of the patch at that point of the chain."""
+
+    def __init__(self, jitter=None, affine=None):
+        self.jitter, self.affine, self.matrix, self.hue_shift = None, None, None, 0
+        if jitter is not None:
+            order, factors, hue = jitter
+            if sorted(order) != [0, 1, 2, 3] or len(factors) != 3:
+                raise ValueError(f"jitter {jitter!r}: the order must be a permutation of 0..3, with three factors and a hue")
+            self.jitter = (tuple(int(o) for o in order), tuple(float(f) for f in factors), float(hue))
+            self.hue_shift = hue_shift(self.jitter[2])
+        if affine is not None:
+            angle, (tx, ty), scale, shear = affine
+            self.affine = (float(angle), (float(tx), float(ty)), float(scale), float(shear))
+
+    def __bool__(self):
+        return self.jitter is not None or self.affine is not None
+
+
+def hue_shift(hue_factor):
+    """adjust_hue's `np.uint8(hue_factor * 255)`: truncated toward zero, modulo 256"""
+    return int(hue_factor * 255) % 256
+
+
+def draw_augmentation(rng, jitter_on, affine_on):
+    """The draws of datasets.py:226-242 from `rng`, in its order (ColorJitter.get_params draws the four factors, then shuffles the ops)."""
+    jitter = affine = None
+    if jitter_on and rng.random() > 0.5:
+        factors = tuple(rng.uniform(0.75, 1.25) for _ in range(3))
+        hue = rng.uniform(-0.04, 0.04)
+        order = [BRIGHTNESS, CONTRAST, SATURATION, HUE]
+        rng.shuffle(order)
+        jitter = (tuple(order), factors, hue)
+    if affine_on and rng.random() > 0:
+        angle = rng.uniform(-10, 10)
+        translate = (rng.uniform(-40, 40), rng.uniform(-40, 40))
+        scale = rng.uniform(0.9, 1.1)
+        shear = rng.uniform(-3, 3)
+        affine = (angle, translate, scale, shear)
+    return Augmentation(jitter, affine)
+
+
+def inverse_affine_matrix(width, height, angle, translate, scale, shear):
+    """torchvision 0.3 F.affine's data for Image.transform(AFFINE): output pixel centre -> input position, about the centre
+    (W / 2 + 0.5, H / 2 + 0.5).  float64 with libm, the form fixed: the device reproduces Pillow only from the same six doubles."""
+    cx, cy = width * 0.5 + 0.5, height * 0.5 + 0.5
+    a, sh = math.radians(angle), math.radians(shear)
+    k = 1.0 / scale
+    d = math.cos(a + sh) * math.cos(a) + math.sin(a + sh) * math.sin(a)
+    m = [math.cos(a + sh), math.sin(a + sh), 0, -math.sin(a), math.cos(a), 0]
+    m = [k / d * v for v in m]
+    m[2] += m[0] * (-cx - translate[0]) + m[1] * (-cy - translate[1])
+    m[5] += m[3] * (-cx - translate[0]) + m[4] * (-cy - translate[1])
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def affine_labels(height, width, labels, angle, translate, scale, shear):
+    """datasets.py affine_labels on corner boxes (float32 [n,5] numpy): float32 torch CPU arithmetic in the reference's sequence of
+    operations (3x3 float32 matrices built from float64 entries, S @ T @ R, the four corners warped, their bounding box shrunk by the
+    angle's reduction and clamped to [0, max(W, H)]); a row is replaced when its warped box passes the size / area / aspect tests."""
+    t = torch.from_numpy(np.array(labels, dtype=_F32))
+    side = max(width, height)
+    alpha = scale * math.cos(math.radians(angle))
+    beta = scale * math.sin(math.radians(angle))
+    rot = torch.tensor(((alpha, beta, (1 - alpha) * (width / 2.0) - beta * (height / 2.0)),
+                        (-beta, alpha, (beta * width / 2.0) + (1 - alpha) * (height / 2.0)),
+                        (0, 0, 1)), dtype=torch.float)
+    tr = torch.eye(3)
+    tr[0, 2] = translate[0]
+    tr[1, 2] = translate[1]
+    sh = torch.eye(3)
+    sh[0, 1] = math.tan(math.radians(shear[0]))
+    sh[0, 2] = -math.tan(math.radians(shear[0])) * height / 2.0
+    sh[1, 0] = math.tan(math.radians(shear[1]))
+    sh[1, 2] = -math.tan(math.radians(shear[1])) * width / 2.0
+    m = sh @ tr @ rot
+    n = t.shape[0]
+    pts = t[:, 1:5]
+    area0 = (pts[:, 2] - pts[:, 0]) * (pts[:, 3] - pts[:, 1])
+    xy = torch.ones((n * 4, 3))
+    xy[:, :2] = pts[:, [0, 1, 2, 3, 0, 3, 2, 1]].reshape(n * 4, 2)
+    xy = xy @ m.transpose(0, 1)
+    xy = xy[:, :2] / xy[:, 2].unsqueeze(1).expand(-1, 2)
+    xy = xy[:, :2].reshape(n, 8)
+    x, y = xy[:, [0, 2, 4, 6]], xy[:, [1, 3, 5, 7]]
+    xy = torch.cat((x.min(1)[0], y.min(1)[0], x.max(1)[0], y.max(1)[0])).reshape(4, n).transpose(0, 1)
+    rad = angle * math.pi / 180
+    reduction = max(abs(math.sin(rad)), abs(math.cos(rad))) ** 0.5
+    cx, cy = (xy[:, 2] + xy[:, 0]) / 2, (xy[:, 3] + xy[:, 1]) / 2
+    w, h = (xy[:, 2] - xy[:, 0]) * reduction, (xy[:, 3] - xy[:, 1]) * reduction
+    xy = torch.cat((cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2)).reshape(4, n).transpose(0, 1)
+    xy = torch.clamp(xy, 0, side)
+    w, h = xy[:, 2] - xy[:, 0], xy[:, 3] - xy[:, 1]
+    area = w * h
+    ar = torch.max(w / (h + 1e-16), h / (w + 1e-16))
+    keep = (w > 4) & (h > 4) & (area / (area0 + 1e-16) > 0.1) & (ar < 10)
+    t[keep, 1:5] = xy[keep]
+    return t.numpy()
+
+
+def aug_descriptor(aug):
+    """MDCV_IMGAUG_DESC ints for one image (include/mdcv_hip.h); `aug` None or empty: the identity, which the kernel copies through"""
+    d = np.zeros(AUG_DESC, np.int32)
+    matrix, order, factors, shift = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0], (0, 1, 2, 3), (1.0, 1.0, 1.0), 0
+    if aug is not None and aug.jitter is not None:
+        order, factors, shift = aug.jitter[0], aug.jitter[1], aug.hue_shift
+        d[12] = 1
+    if aug is not None and aug.affine is not None:
+        if aug.matrix is None:
+            raise ValueError("an affine augmentation needs its matrix (inverse_affine_matrix) before it is packed")
+        matrix = aug.matrix
+        d[21] = 1
+    d[0:12] = np.array(matrix, np.float64).view(np.int32)
+    d[13:17] = order
+    d[17:20] = np.array(factors, _F32).view(np.int32)           # Image.blend takes its alpha as a C float
+    d[20] = shift
+    return d
+
+
 # ----------------------------------------------------------------------------------------------------------- labels (host, exact)
 def _t(a, b):            # a 0-dim float32 tensor meeting a Python number: the number is rounded to float32 first
     if isinstance(a, np.float32) or isinstance(b, np.float32):
@@ -268,8 +409,9 @@ def filter_and_offset_labels(labels, boundary):
     return np.zeros((len(labels), 5), _F32)
 
 
-def sample_labels(boxes, geom, num_targets):
-    """ImageLabelDataset.__getitem__'s label half for raw CSV boxes [n,4] (x, y, h, w) -> float32 [num_targets, 5] (cls, cx, cy, w, h)."""
+def sample_labels(boxes, geom, num_targets, aug=None):
+    """ImageLabelDataset.__getitem__'s label half for raw CSV boxes [n,4] (x, y, h, w) -> float32 [num_targets, 5] (cls, cx, cy, w, h).
+    `aug` with an affine: the boxes are warped between the patch offset / letterbox scale and the flip, as in the reference."""
     boxes = np.asarray(boxes, _F32).reshape(-1, 4)
     out = np.zeros((num_targets, 5), _F32)
     if len(boxes) == 0:
@@ -284,6 +426,9 @@ def sample_labels(boxes, geom, num_targets):
     else:
         l[:, 1:5] = l[:, 1:5] + np.array([geom.pad_w, geom.pad_h, geom.pad_w, geom.pad_h], _F32)
         l[:, 1:5] = _F32(geom.ratio) * l[:, 1:5]
+    if aug is not None and aug.affine is not None:
+        angle, translate, scale, shear = aug.affine
+        l = affine_labels(geom.height, geom.width, l, -angle, translate, scale, (-shear, 0))
     if geom.flip:
         l[:, 1] = _F32(geom.width) - l[:, 1]
         l[:, 3] = _F32(geom.width) - l[:, 3]
@@ -327,7 +472,8 @@ class _Packed:
 
 
 def pack_layout(geoms, windows_nbytes, num_targets):
-    """Byte layout of one batch's staging buffer: [descriptors][labels][coefficient tables][pixels]."""
+    """Byte layout of one batch's staging buffer: [descriptors][labels][coefficient tables][pixels], and behind them, only when a
+    sample of the batch is augmented, [augmentation descriptors] (a batch without one is laid out exactly as before)."""
     p = _Packed()
     B = len(geoms)
     p.B, p.T = B, num_targets
@@ -338,6 +484,10 @@ def pack_layout(geoms, windows_nbytes, num_targets):
     p.pix_off = _align(p.coef_off + p.n_coefs * 4)
     p.src_bytes = sum(windows_nbytes)
     p.nbytes = _align(p.pix_off + p.src_bytes)
+    p.aug = any(bool(getattr(g, "aug", None)) for g in geoms)
+    if p.aug:
+        p.aug_off = p.nbytes
+        p.nbytes = _align(p.aug_off + B * AUG_DESC * 4)
     p.max_scr_w = max(g.desc[7] for g in geoms)
     p.max_scr_h = max(g.desc[8] for g in geoms)
     return p
@@ -360,18 +510,33 @@ def pack_batch(buf, p, geoms, windows, labels=None):
         desc[b] = d
         buf[p.pix_off + s:p.pix_off + s + w.nbytes] = w.reshape(-1)
         s += w.nbytes
+    if p.aug:
+        aug = buf[p.aug_off:p.aug_off + p.B * AUG_DESC * 4].view(np.int32).reshape(p.B, AUG_DESC)
+        for b, g in enumerate(geoms):
+            aug[b] = aug_descriptor(getattr(g, "aug", None))
     if p.T and labels is not None:
         buf[p.lab_off:p.lab_off + p.B * p.T * 20].view(np.float32)[:] = np.asarray(labels, np.float32).reshape(-1)
 
 
 def launch_batch(dev_buf, host_buf, p, channels, height, width, stream):
-    """Enqueue the kernel pair on `stream` for a staged batch already copied to `dev_buf` (device uint8) -> imgs [B,C,H,W]."""
+    """Enqueue the kernels on `stream` for a staged batch already copied to `dev_buf` (device uint8) -> imgs [B,C,H,W]: the pair of
+    csrc/imgload.hip, or csrc/imgaug.hip's sequence when the batch carries augmentation descriptors."""
     L = _lib.lib()
     dev = dev_buf.device
     imgs = torch.empty(p.B, channels, height, width, dtype=torch.float32, device=dev)
     wsb = L.imgload_workspace_bytes(p.B, p.max_scr_w, p.max_scr_h)
     ws = torch.empty(max(int(wsb), 1), dtype=torch.uint8, device=dev)
     base = dev_buf.data_ptr()
+    if p.aug:
+        awb = L.imgaug_workspace_bytes(p.B, height, width)
+        if awb < 0:
+            raise ValueError(f"augmented batches need 0 < H * W <= 4096 * 4096, got {height}x{width}")
+        aws = torch.empty(int(awb), dtype=torch.uint8, device=dev)
+        hb = host_buf.ctypes.data
+        L.check(L.imgload_aug_batch(hb + p.desc_off, base + p.desc_off, hb + p.aug_off, base + p.aug_off, p.B, base + p.coef_off, p.n_coefs,
+                                    base + p.pix_off, p.src_bytes, p.max_scr_w, p.max_scr_h, channels, height, width, ws.data_ptr(),
+                                    aws.data_ptr(), imgs.data_ptr(), stream.cuda_stream), "imgload_aug_batch")
+        return imgs
     L.check(L.imgload_batch(host_buf.ctypes.data + p.desc_off, base + p.desc_off, p.B, base + p.coef_off, p.n_coefs, base + p.pix_off,
                             p.src_bytes, p.max_scr_w, p.max_scr_h, channels, height, width, ws.data_ptr(), imgs.data_ptr(),
                             stream.cuda_stream), "imgload_batch")
@@ -379,7 +544,8 @@ def launch_batch(dev_buf, host_buf, p, channels, height, width, stream):
 
 
 def transform_batch(frames, geoms, bw=False, device=None):
-    """Synchronous convenience (tests, probes): decoded frames [(H, W, 3) uint8] + their geometries -> imgs [B,C,H,W] fp32 on the device."""
+    """Synchronous convenience (tests, probes): decoded frames [(H, W, 3) uint8] + their geometries (each may carry `.aug`, an
+    `Augmentation` with its matrix set) -> imgs [B,C,H,W] fp32 on the device."""
     _lib.require_gpu()
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     windows = [crop_window(f, g) for f, g in zip(frames, geoms)]
@@ -406,7 +572,9 @@ class ImageLabelBatches:
     `DataLoader(ImageLabelDataset(path, dataset_path, width, height, ..., num_images, bw, lr_flip, ts), batch_size, shuffle)` yields.
 
     `decode(path)` -> a PIL image or an (H, W, 3) uint8 array (default: `PIL.Image.open(path).convert('RGB')`), run on `num_workers`
-    threads.  `draws(epoch, index)` -> (patch_index, flip) overrides the random draws (tests).  `subset_seed` seeds the
+    threads.  `augment_hsv` / `augment_affine` / `data_aug` (both) turn on the reference's ColorJitter / affine augmentation.
+    `draws(epoch, index)` -> (patch_index, flip) or (patch_index, flip, aug) overrides the random draws (tests); `aug` is None, an
+    `Augmentation`, or a dict with `jitter` and / or `affine` in `Augmentation`'s form; when it is left out the augmentation stays as drawn.  `subset_seed` seeds the
     `random.sample` of `num_images`; its default 0 is the `random.seed(0)` that CVC-YOLOv3/train.py:40 runs before it builds its
     loaders, so the training loader's subset is the one train.py draws.  `debug_mode` forces patch 0 as the reference does (the patch
     draw still happens first, so the flip draw is unchanged).  With `prefetch`, batch i+1 is decoded and
@@ -415,17 +583,17 @@ class ImageLabelBatches:
 
     def __init__(self, path, dataset_path, width, height, num_images=-1, bw=False, lr_flip=False, ts=True, batch_size=1, shuffle=True,
                  num_workers=None, seed=0, device=None, decode=None, ud_flip=False, subset_seed=0, draws=None, prefetch=True, debug_mode=False,
-                 **options):
+                 augment_hsv=False, augment_affine=False, data_aug=False, **options):
         bad = [k for k in UNSUPPORTED if options.pop(k, False)]
         if bad:
-            raise ValueError(f"ImageLabelBatches does not implement {', '.join(bad)} (torchvision 0.3 / imgaug augmentations); "
-                             "set them False")
+            raise ValueError(f"ImageLabelBatches does not implement {', '.join(bad)} (imgaug augmentations); set them False")
         for k in ("vis_batch", "upload_dataset", "n_cpu"):
             options.pop(k, None)
         if options:
             raise TypeError(f"ImageLabelBatches: unknown arguments {sorted(options)}")
         self.width, self.height, self.bw, self.lr_flip, self.ts = int(width), int(height), bool(bw), bool(lr_flip), bool(ts)
         self.ud_flip = ud_flip                                   # accepted and ignored, as in the reference
+        self.augment_hsv, self.augment_affine, self.data_aug = bool(augment_hsv), bool(augment_affine), bool(data_aug)
         self.debug_mode = bool(debug_mode)
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
         self.num_workers = int(num_workers) if num_workers is not None else max(1, min(16, os.cpu_count() or 1))
@@ -464,19 +632,31 @@ class ImageLabelBatches:
         return idx
 
     def plan(self, index, epoch=0, frame_size=None):
-        """Host-only: the draws, geometry and labels of sample `index` in `epoch` (frame_size: the decoded (W, H); default the CSV's)."""
+        """Host-only: the draws, geometry, augmentation (`.aug`: None or an `Augmentation` with its matrix) and labels of sample `index`
+        in `epoch` (frame_size: the decoded (W, H); default the CSV's)."""
         w, h = frame_size if frame_size is not None else self.sizes[index]
         rng = random.Random(f"{self.seed}/{epoch}/{index}")
         patch = rng.randint(0, n_patches(w, h, self.scales[index], self.width, self.height) - 1) if self.ts else 0
         if self.debug_mode:
             patch = 0
-        flip = bool(self.lr_flip and len(self.labels[index]) > 0 and rng.random() > 0.5)
+        boxed = len(self.labels[index]) > 0                          # raw-empty samples return before the augmentation and the flip
+        aug = None
+        if boxed and (self.augment_hsv or self.augment_affine or self.data_aug):
+            aug = draw_augmentation(rng, self.augment_hsv or self.data_aug, self.augment_affine or self.data_aug)
+        flip = bool(self.lr_flip and boxed and rng.random() > 0.5)
         if self.draws is not None:
-            patch, flip = self.draws(epoch, index)
-            flip = bool(flip) and len(self.labels[index]) > 0        # raw-empty samples return before the flip
+            d = self.draws(epoch, index)
+            patch, flip = d[0], bool(d[1]) and boxed
+            if len(d) > 2:
+                aug = d[2] if boxed else None
+                if isinstance(aug, dict):
+                    aug = Augmentation(aug.get("jitter"), aug.get("affine"))
+        if aug is not None and aug.affine is not None:
+            aug.matrix = inverse_affine_matrix(self.width, self.height, *aug.affine)
         g = sample_geometry(w, h, self.width, self.height, self.ts, self.scales[index] if self.ts else 1.0, patch, flip)
         g.index, g.uri = index, self.img_files[index]
-        g.labels = sample_labels(self.labels[index], g, self.num_targets_per_image)
+        g.aug = aug if aug else None
+        g.labels = sample_labels(self.labels[index], g, self.num_targets_per_image, g.aug)
         return g
 
     # -- host half: decode, plan, crop, stage

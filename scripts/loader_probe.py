@@ -3,10 +3,13 @@
 (a) the device transform alone: ms per B=32 batch of 416x416 outputs from pre-decoded, pre-staged 1920x1080-class frames
     (LANCZOS tile-and-scale at scale 0.5 / 1.0 / 1.5; BILINEAR pad-and-resize of a frame of 1920s x 1080s for the same s)
 (b) the whole loader with decode, img/s on 1 / 8 / 16 decode threads, PNG and JPEG files written to a temporary directory
-(c) ms per YOLOv3 416x416 B=32 bf16 train step fed by the loader against the same step fed by SyntheticCones
+(c) ms per YOLOv3 416x416 B=32 bf16 train step fed by the loader (plain, and with data_aug=True) against the same step fed by SyntheticCones
+(d) the augmented transform (csrc/imgaug.hip) alone, B=32 of 416x416 from 1920x1080 frames, tile-and-scale at scale 1.0: no augmentation
+    (the two-launch path), affine only, jitter + affine as data_aug draws them; each row several times over to show the run-to-run spread
 
-Device events after a warm-up, profiler off.  usage: loader_probe.py [files per format (default 32)]"""
+Device events after a warm-up, profiler off.  usage: loader_probe.py [files per format (default 32)] [parts, default abcd]"""
 import contextlib
+import ctypes
 import io
 import os
 import random
@@ -26,6 +29,7 @@ from mdcv.data.synth import SyntheticCones  # noqa: E402
 
 B, S = 32, 416
 NFILES = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+PARTS = sys.argv[2] if len(sys.argv) > 2 else "abcd"
 
 
 def frame(seed, w=1920, h=1080):
@@ -160,16 +164,66 @@ def part_c(tmp, csv_path, steps=10):
         real = run(ld)
         ld.close()
         print(f"    SyntheticCones: {syn:7.2f} ms/step   ImageLabelBatches (JPEG, {t:2d} threads): {real:7.2f} ms/step")
+    ld = I.ImageLabelBatches(csv_path, tmp, S, S, ts=True, lr_flip=True, batch_size=B, num_workers=16, data_aug=True)
+    real = run(ld)
+    ld.close()
+    print(f"    SyntheticCones: {syn:7.2f} ms/step   ImageLabelBatches (JPEG, 16 threads, data_aug): {real:7.2f} ms/step")
+
+
+def part_d(frames, repeats=5):
+    print("(d) augmented transform alone, B=32 outputs of 416x416 RGB from 1920x1080 frames, tile-and-scale at scale 1.0 "
+          f"(ms per batch, kernels only; {repeats} timings of 50 batches each)")
+    patch_mb = B * S * S * 4 / 1e6                           # one pass over the uint8 RGBX patches
+    out_mb = B * 3 * S * S * 4 / 1e6
+    for name, jit_on, aff_on in (("none (two launches)", False, False), ("affine only", False, True), ("jitter + affine", True, True)):
+        geoms, wins = [], []
+        for b in range(B):
+            f = frames[b % len(frames)]
+            rng = random.Random(f"probe/{b}")
+            g = I.sample_geometry(f.shape[1], f.shape[0], S, S, True, 1.0, rng.randrange(I.n_patches(f.shape[1], f.shape[0], 1.0, S, S)), b % 2)
+            aug = I.draw_augmentation(rng, jit_on, aff_on)
+            if aug.affine is not None:
+                aug.matrix = I.inverse_affine_matrix(S, S, *aug.affine)
+            g.aug = aug if aug else None
+            geoms.append(g)
+            wins.append(I.crop_window(f, g))
+        p = I.pack_layout(geoms, [w.nbytes for w in wins], 0)
+        host = np.zeros(p.nbytes, np.uint8)
+        I.pack_batch(host, p, geoms, wins)
+        dev = torch.from_numpy(host).cuda()
+        st = torch.cuda.current_stream()
+        ms = sorted(ev_ms(lambda: I.launch_batch(dev, host, p, 3, S, S, st), 50) for _ in range(repeats))
+        n_jit = sum(g.aug is not None and g.aug.jitter is not None for g in geoms)
+        # bytes the augmentation adds: the patch written once, read by the statistics pass (jittered images) and by the apply pass
+        moved = patch_mb * (2 + n_jit / B) + out_mb if p.aug else 0.0
+        print(f"    {name:20s}: median {ms[len(ms) // 2]:7.3f} ms/batch  min {ms[0]:7.3f}  max {ms[-1]:7.3f}   jittered {n_jit:2d}/{B}"
+              + (f"   patch + output traffic {moved:6.1f} MB" if p.aug else ""))
+        L = I._lib.lib()                                         # one more batch under the in-library profiler: each kernel's own time
+        torch.cuda.synchronize()
+        L.profile_begin()
+        I.launch_batch(dev, host, p, 3, S, S, st)
+        torch.cuda.synchronize()
+        for i in range(L.profile_stop()):
+            t, buf = ctypes.c_float(), ctypes.create_string_buffer(256)
+            L.profile_read(i, ctypes.byref(t), buf, 256)
+            name = buf.value.decode().split("::")[-1].split("(")[0]
+            print(f"        {name:32s} {1e3 * t.value:8.1f} us")
 
 
 def main():
     torch.cuda.set_device(0)
     frames = [frame(i) for i in range(8)]
-    part_a(frames)
-    with tempfile.TemporaryDirectory() as tmp:
-        csvs = {fmt: write_dataset(tmp, frames, fmt) for fmt in ("png", "jpg")}
-        part_b(tmp, csvs)
-        part_c(tmp, csvs["jpg"])
+    if "a" in PARTS:
+        part_a(frames)
+    if "d" in PARTS:
+        part_d(frames)
+    if "b" in PARTS or "c" in PARTS:
+        with tempfile.TemporaryDirectory() as tmp:
+            csvs = {fmt: write_dataset(tmp, frames, fmt) for fmt in (("png", "jpg") if "b" in PARTS else ("jpg",))}
+            if "b" in PARTS:
+                part_b(tmp, csvs)
+            if "c" in PARTS:
+                part_c(tmp, csvs["jpg"])
 
 
 if __name__ == "__main__":
