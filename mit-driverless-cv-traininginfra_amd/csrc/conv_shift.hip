@@ -1,6 +1,6 @@
 // 3x3 / stride 1 / pad = dilation convolution (forward and data gradient) as NINE SHIFTED GEMMs over one LDS-resident activation chunk.
 //
-// Why: the im2col kernel (conv_igemm.hip) fills LDS with a fresh A tile for every tap, i.e. every activation pixel travels
+// Why: the im2col kernel (conv_gemm.h) fills LDS with a fresh A tile for every tap, i.e. every activation pixel travels
 // L2 -> LDS nine times.  Measured on MI355X that fill path saturates at ~30 GB/s per CU (~12.6 B/clk/CU), which is exactly what
 // holds the 3x3 layers at ~650 TFLOP/s (24 KiB of fill per 256x128x32 MACs).  Here the pixels of a tile are filled ONCE per
 // 32-channel chunk and all nine taps read them at shifted LDS rows, so the fill per K step drops from 24 KiB to 2.6 + 8 KiB.

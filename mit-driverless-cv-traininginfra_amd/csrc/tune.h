@@ -8,7 +8,7 @@
 #pragma once
 
 struct MdcvTune {
-  // ---- conv_igemm.hip
+  // ---- conv_gemm.h (conv_*: tile dispatch), wgrad_gemm.hip and the family chooser of conv_igemm.hip (wgrad_*)
   int conv_no_ut = 0;   // tuning/A-B: 1 disables the uniform-tap address path
   int conv_tall_narrow = 256;   // 256-row tiles for Nout <= 64 from this many Ki output positions (set_variant 2000 + M_min/1024; 2000 = off): half as
       // many workgroup prologues / epilogues on the 80^2 x 256 and 208^2..416^2 x 32 tensors.  Same-box A/B: RektNet +0.65 %, YOLOv3 +0.2 %
@@ -30,7 +30,7 @@ struct MdcvTune {
       // HBM-latency-bound with little work per step: it wants blocks, not depth.  416^2 x 32 at batch 32, alone (scripts/bna_ab.py), stages 2 / 3 / 4:
       // 258 / 262 / 391 us at the generic target of 512 blocks (four stages = 96 KiB leave room for ONE block per CU: two rounds),
       // 191 / 267 / 388 us at 768 blocks (three two-stage blocks per CU in one round; the plan asks for that split count, engine.emit_first_conv_bwd)
-  int wgrad_variant = 0;   // 0: default dispatch ; 4: generic address path ; 5: wide tile everywhere ; 8 / 9 / 10 / 11: kernel-family choices (use_wgrad_*)
+  int wgrad_variant = 0;   // 0: default dispatch ; 4: generic address path ; 5: wide tile everywhere ; 8 / 9 / 10 / 11: kernel-family choices (wgrad_eligible, conv_igemm.hip)
   // ---- conv_shift.hip
   int shift_ring = 4;   // weight-ring depth of sparse grids (<= 256 tiles); 3: off (tuning hook: mdcv_conv2d_set_variant(-3 / -4))
   int shift_wmax_narrow = 104;   // rows up to 104 pixels for the 64- / 32-wide tiles (their smaller weight ring keeps two workgroups on a CU): the data gradients of
@@ -121,7 +121,7 @@ inline void mdcv_tune_apply_conv(MdcvTune& t, int v) {
   if (v >= 100) { t.conv_no_ut = 1; v -= 100; }              // 100 + v: variant v with the generic address path
   if (v >= 1 && v <= 12) t.conv_variant = v - 1;
 }
-// weight-gradient family.  0: defaults ; 4: generic address path ; 5: wide tile everywhere ; 8 / 9 / 10 / 11: kernel-family choices (use_wgrad_*) ;
+// weight-gradient family.  0: defaults ; 4: generic address path ; 5: wide tile everywhere ; 8 / 9 / 10 / 11: kernel-family choices (wgrad_eligible, conv_igemm.hip) ;
 // 1000 + 100 d + blocks/64: LDS-ring kernel with d & 8 = untiled and a forced block target ; 20000 + n: block target of the generic kernel ;
 // 30000 + n: block target of the 8-wave tiled LDS-ring form (30002: default form choice, 30003: light form everywhere, 30005: never) ;
 // 33000 + n: the light form's block target

@@ -1,4 +1,4 @@
-// Internal interface between conv_igemm.hip (mdcv_conv2d_wgrad) and wgrad_shift.hip (3x3 stride-1 weight gradient, kw taps sharing a tile).
+// Internal interface between conv_igemm.hip (mdcv_conv2d_wgrad, family WG_SHIFT of its chooser) and wgrad_shift.hip (3x3 stride-1 weight gradient, kw taps sharing a tile).
 #pragma once
 #include <hip/hip_runtime.h>
 

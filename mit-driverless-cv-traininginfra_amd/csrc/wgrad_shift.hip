@@ -1,6 +1,6 @@
 // Weight gradient of a 3x3 / stride 1 / pad 1 convolution with the three kw taps of a kernel row sharing ONE activation tile.
 //
-// The generic weight-gradient kernel (conv_igemm.hip, conv_wgrad_dma_kernel) is bound by the global->LDS fill path: a
+// The generic weight-gradient kernel (wgrad_gemm.hip, conv_wgrad_dma_kernel) is bound by the global->LDS fill path: a
 // 128(co) x 128(k) block fills a 16 KiB dY tile and a 16 KiB im2col tile per 64 pixels = 65 FLOP per filled byte, which holds the
 // MFMA pipe at ~20 %.  The im2col tiles of the taps (kh, 0), (kh, 1), (kh, 2) are the same activation rows shifted by one pixel,
 // so here a block owns co-tile x ci-tile x {3 kw taps}: per 64 positions it fills the dY tile once and ONE activation tile of 64+2
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_shift_kernel(WgradShiftArgs a, u
     const int c = 2 * F + qlo;
     const int g0 = 2 * (row0 & 7);
     const unsigned ad = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)tile + (unsigned)(row0 * 256 + ((c ^ g0) << 4) + sub);
-    const s16x4_t lo = lds_tr16_asm<0>(ad);                    // asm reads: see conv_igemm.hip (no compiler-forced DMA drain)
+    const s16x4_t lo = lds_tr16_asm<0>(ad);                    // asm reads: see wgrad_gemm.hip (no compiler-forced DMA drain)
     const s16x4_t hi = lds_tr16_asm<16 * 256>(ad);
     typedef __attribute__((ext_vector_type(8))) short s16x8_t;
     const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};

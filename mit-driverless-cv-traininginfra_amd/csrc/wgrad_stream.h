@@ -1,4 +1,4 @@
-// Internal interface between conv_igemm.hip (mdcv_conv2d_wgrad) and wgrad_stream.hip: 3x3 stride-1 "same" weight gradient
+// Internal interface between conv_igemm.hip (mdcv_conv2d_wgrad, families WG_STEM / WG_STREAM / WG_S2 of its chooser) and wgrad_stream.hip: 3x3 stride-1 "same" weight gradient
 // (dilation 1 or 2) for 16..128-channel layers, activation window kept in an LDS ring.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // Weight gradient of a 3x3 / stride 1 / "same" convolution (dilation 1 or 2) for the 16..128-channel layers, with the activation
 // window of ALL NINE taps resident in an LDS ring.
 //
-// Why: the generic kernel (conv_igemm.hip, conv_wgrad_dma_kernel / _narrow_kernel) gathers an im2col tile per tap, so every activation
+// Why: the generic kernel (wgrad_gemm.hip, conv_wgrad_dma_kernel / _narrow_kernel) gathers an im2col tile per tap, so every activation
 // row travels through the global->LDS path nine times.  For C <= 64 that path, not HBM and not the MFMA pipe, sets the time
 // (RektNet 80x80 16->16: 118 us for 105 MB of operands = 0.9 TB/s; 64->64: 287 TFLOP/s), and a 128-wide output-channel tile wastes
 // half its MFMAs on Cout = 64.

@@ -1,7 +1,7 @@
 // Weight gradient of a 3x3 / STRIDE 2 / pad 1 convolution (even input, Hin = 2 Hout): the down-sampling layers of Darknet-53
 // (reference models.py create_modules: every "stride=2" [convolutional] block), on the LDS-ring scheme of wgrad_stream.hip.
 //
-// Why: the generic kernel (conv_igemm.hip, conv_wgrad_dma_kernel) gathers an im2col tile per tap -- 250 MB fetched per launch for 60-90 MB of operands,
+// Why: the generic kernel (wgrad_gemm.hip, conv_wgrad_dma_kernel) gathers an im2col tile per tap -- 250 MB fetched per launch for 60-90 MB of operands,
 // 100-135 us alone and 230 us inside the step for 51 GFLOP (the stride-1 layers with the same FLOPs take 55 us alone).
 //
 // Stride 2 as a stride-1 problem: cut the input into its four PARITY PLANES, XP[py][px][img][oy][ox] = X[img][2 oy + py][2 ox + px] (space to depth, never

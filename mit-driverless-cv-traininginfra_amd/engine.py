@@ -665,7 +665,7 @@ class Plan:
         return (dy1, dy2) if y2 is not None else dy1
 
     # ---- first layer (its input needs no gradient): dy = BatchNorm-backward(dz, y) has the weight gradient as its ONLY reader, so it is formed in
-    # that kernel's operand load (mdcv_conv2d_wgrad_bnapply, conv_igemm.hip BNA) and the apply pass over the network's largest tensor never runs.
+    # that kernel's operand load (mdcv_conv2d_wgrad_bnapply, wgrad_gemm.hip BNA) and the apply pass over the network's largest tensor never runs.
     # YOLOv3 416^2 batch 32: apply 193 us on the main queue + weight gradient 131 us alone behind it, at the exposed tail of the backward.
     wgrad_bnapply = True               # (tests / scripts/ab_step.py flip the class attribute; no environment knob)
     first_conv_2pass = True            # the first conv's forward as two streaming passes over its INPUT (csrc/first_conv.hip; yolo/models.py)
