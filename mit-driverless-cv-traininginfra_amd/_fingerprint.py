@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def fingerprint_files():
-    pats = ["csrc/*.hip", "csrc/*.h", "csrc/*.inc", "csrc/Makefile", "engine.py", "_lib.py", "yolo/models.py", "rektnet/keypoint_net.py",
+    pats = ["csrc/*.hip", "csrc/*.h", "csrc/*.inc", "csrc/Makefile", "engine.py", "netplan.py", "_lib.py", "yolo/models.py", "yolo/lower.py", "rektnet/keypoint_net.py",
             "rektnet/resnet.py", "optim.py", "pipeline.py", "parallel.py"]
     out = []
     for p in pats:

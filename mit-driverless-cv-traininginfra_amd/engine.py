@@ -321,9 +321,12 @@ class Plan:
             t.gstate = "own"
         else:
             a = t.grad
-        o = t.grad
-        self.call(self.bwd, self.L.bn_act_fwd, self.dtype, a.ptr, a.ldc, None, None, None, 0, None, None, src.ptr, src.ldc,
-                  o.ptr, o.ldc, o.M, o.C, ACT_NONE, 0.0)
+        self.emit_add(self.bwd, a, src, t.grad)
+
+    def emit_add(self, lst, a, b, out):
+        """out = a + b on Acts of one shape; b=None: out = a (the BatchNorm-apply kernel without coefficients or activation)"""
+        self.call(lst, self.L.bn_act_fwd, self.dtype, a.ptr, a.ldc, None, None, None, 0, None, None, b.ptr if b is not None else None,
+                  b.ldc if b is not None else 0, out.ptr, out.ldc, out.M, out.C, ACT_NONE, 0.0)
 
     def _alloc_like(self, a):
         return self.new_act(a.B, a.H, a.W, a.C)

@@ -19,7 +19,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..engine import TNode, ConvSpec, BnSpec, parse_precision, ACT_RELU, BF16
-from ..yolo.models import _NetPlan, FlatParamsMixin, _bump_counters, _sync_before_state_dict, _EVAL_FUSE
+from .. import netplan
+from ..netplan import _NetPlan, FlatParamsMixin, _bump_counters, _sync_before_state_dict
 from .resnet import ResNet, lower_conv_bn, lower_block, lower_block_bwd
 
 
@@ -147,35 +148,32 @@ class KeypointNet(FlatParamsMixin, nn.Module):
             hm, pts = hm * 0.0, pts * 0.0
         return hm, pts.view(-1, self.num_kpt, 2)
 
+    @staticmethod
+    def _emit_input16(plan, B, H, W):
+        """second copy of the input with 16-channel rows: the stem's weight gradient runs the LDS-ring kernel on it (csrc/wgrad_stream.hip)"""
+        L, dt, holder = plan.L, plan.dtype, plan.in_holder
+        x16 = plan.new_act(B, H, W, 16)
+
+        def convert16(stream):
+            return L.nchw_to_nhwc(dt, holder["src"].data_ptr(), x16.ptr, B, 3, H, W, x16.ldc, x16.C, stream)
+        convert16.__name__ = "nchw_to_nhwc"
+        plan.pre.append((convert16, ()))
+        return x16
+
     def _build_plan(self, device, B, H, W, bn_train, logits_only, infer=False):
-        plan = _KpPlan(device, self.precision, bn_train, grad_sink=self._grad_view)
-        plan.owner = self
-        plan.grad_offset = lambda p: self._goff[id(p)][0]
-        plan.use_graph = self.use_graph
+        plan, xin = _KpPlan.begin(self, device, bn_train, B, 3, H, W, self.use_graph)
         plan.graphs_bwd = {}
         plan._dhm = None
-        plan.pre = []
         L, dt = plan.L, plan.dtype
         K = self.num_kpt
-        xin, holder = plan.emit_input(B, 3, H, W)
-        plan.pre.append(plan.fwd.pop())
-        plan.in_holder = holder
         plan.x16 = None
         if bn_train and not logits_only and plan.dtype == BF16 and self.conv.kernel_size == (7, 7) and self.conv.padding == (3, 3) \
                 and self.conv.out_channels == 16:
-            # second copy of the input with 16-channel rows: the stem's weight gradient runs the LDS-ring kernel on it (csrc/wgrad_stream.hip)
-            x16 = plan.new_act(B, H, W, 16)
-            plan.x16 = x16
-
-            def convert16(stream, x16=x16):
-                return L.nchw_to_nhwc(dt, holder["src"].data_ptr(), x16.ptr, B, 3, H, W, x16.ldc, x16.C, stream)
-            convert16.__name__ = "nchw_to_nhwc"
-            plan.pre.append((convert16, ()))
-        plan.targets = None
+            plan.x16 = self._emit_input16(plan, B, H, W)
         nbt = []
         recs = []
 
-        one_launch = infer and _EVAL_FUSE
+        one_launch = infer and netplan._EVAL_FUSE
 
         def conv_bn(conv, bn, xnode, relu_into=None):
             return lower_conv_bn(plan, conv, bn, xnode, B, H, W, bn_train, nbt, one_launch, relu_into=relu_into)

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..engine import TNode, ConvSpec, BnSpec, parse_precision, ACT_RELU
-from ..yolo.models import _NetPlan, FlatParamsMixin, _bump_counters, _sync_before_state_dict
+from ..netplan import _NetPlan, FlatParamsMixin, _bump_counters, _sync_before_state_dict
 
 
 def lower_conv_bn(plan, conv, bn, xnode, B, H, W, bn_train, nbt, one_launch=False, relu_into=None):
@@ -138,16 +138,8 @@ class ResNet(FlatParamsMixin, nn.Module):
         return plan.out_nchw.clone()
 
     def _build_plan(self, device, B, H, W, bn_train, with_bwd, need_dx):
-        plan = _BlockPlan(device, self.precision, bn_train, grad_sink=self._grad_view)
-        plan.owner = self
-        plan.grad_offset = lambda p: self._goff[id(p)][0]
-        plan.use_graph = False
-        plan.pre = []
+        plan, xin = _BlockPlan.begin(self, device, bn_train, B, self.in_channels, H, W, use_graph=False)
         L, dt = plan.L, plan.dtype
-        xin, holder = plan.emit_input(B, self.in_channels, H, W)
-        plan.pre.append(plan.fwd.pop())
-        plan.in_holder = holder
-        plan.targets = None
         xin.needs_grad = need_dx
         nbt = []
         rec, out = lower_block(plan, self, xin, B, H, W, bn_train, nbt)

@@ -38,12 +38,12 @@ def apply_build(codes):
     engine.Plan.wgrad_bnapply = True
     engine.Plan.first_conv_2pass = True
     engine.Plan.pw_fwd_px = (50000, 1 << 30)
-    from mdcv.yolo import models as _ym0
+    from mdcv import netplan as _ym0
     _ym0._NetPlan.fork_on_dispatch = True
     _ym0._NetPlan.defer_slab_reduce = True
     for c in codes:
         if c and c[0] == "K":          # K0 / K1: side-stream forks as event records on the main queue / carried by the producing kernel's dispatch packet
-            from mdcv.yolo import models as _ym
+            from mdcv import netplan as _ym
             _ym._NetPlan.fork_on_dispatch = bool(int(c[1:]) & 1)
             _ym._NetPlan.defer_slab_reduce = not bool(int(c[1:]) & 2)               # K3: forks on dispatch, slab reduces NOT deferred
         if c and c[0] == "c":

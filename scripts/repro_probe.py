@@ -5,7 +5,7 @@ import os, sys, tempfile, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench
-from mdcv.yolo import models as M
+from mdcv import netplan as M
 from mdcv.yolo.models import Darknet
 from mdcv.optim import FusedAdam
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 200

@@ -150,13 +150,14 @@ def _auto_uneven(rank, world):
 
 def _yolo_full(rank, world, defer):
     """the full yolo_baseline (bf16, 416^2, two images per rank): the one-launch 1x1 backward's slab reduces are DEFERRED on the side stream
-    (mdcv/yolo/models.py run_bwd_list) and, under data parallel, flushed in front of every marker that starts a bucket"""
+    (mdcv/netplan.py run_bwd_list) and, under data parallel, flushed in front of every marker that starts a bucket"""
     import tempfile
     sys.path.insert(0, ROOT)
     import bench
+    from mdcv import netplan
     from mdcv.yolo import models as ym
     from mdcv.parallel import GradAllReducer
-    ym._NetPlan.defer_slab_reduce = bool(defer)
+    netplan._NetPlan.defer_slab_reduce = bool(defer)
     tmp = tempfile.mkdtemp(prefix=f"mdcv_dp{rank}_")
     cfg = bench.write_yolo_cfg(tmp)
     os.chdir(tmp)

@@ -407,3 +407,75 @@ def test_bench_comm_preflight_turns_a_failing_lease_into_a_diagnosis():
     d = json.loads(line)
     assert d["error"] == "data-parallel preflight failed" and d["step"] == "init_process_group" and d["world"] == 2 and d["backend"] == "nccl"
     assert "exception" in d and "hint" in d and "HSA_ENABLE_IPC_MODE_LEGACY" in d
+
+
+def _reference_shapes(net, size):
+    """(C, H, W) per section from the stock nn modules on a batch-1 zero tensor: route = torch.cat, shortcut = add (reference models.py:312-338)."""
+    x = torch.zeros(1, int(net.hyperparams["channels"]), size, size)
+    outs = []
+    with torch.no_grad():
+        for i, (d, m) in enumerate(zip(net.module_defs, net.module_list)):
+            k = d["type"]
+            if k in ("convolutional", "upsample", "maxpool"):
+                x = m(x)
+            elif k == "route":
+                x = torch.cat([outs[i + int(t) if int(t) < 0 else int(t)] for t in d["layers"].split(",")], 1)
+            elif k == "shortcut":
+                x = outs[-1] + outs[i + int(d["from"]) if int(d["from"]) < 0 else int(d["from"])]
+            outs.append(x)                                   # ([yolo] passes its input on)
+    return [tuple(o.shape[1:]) for o in outs]
+
+
+def test_darknet_graph_analysis_shapes_concat_layout_and_guards(tmp_path):
+    """yolo/lower.py analyse() is a pure host function of the cfg: its per-section (C, H, W) against the stock nn modules run on the CPU,
+    its concat layout (every producer's slice tiles the route buffer in `layers=` order, no overlap), and its two guards."""
+    from mdcv.yolo.models import Darknet
+    from mdcv.yolo.lower import analyse
+    from mdcv.engine import pad8
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_models import write_baseline_cfg
+
+    def build(cfg, where):
+        cwd = os.getcwd()
+        os.chdir(where)
+        try:
+            return Darknet(cfg, 2.0, 1.6, 25.0, 0.1, True)
+        finally:
+            os.chdir(cwd)
+    full = write_baseline_cfg(str(tmp_path), 416, 80)
+    cases = [(n + ".cfg", os.path.join(G, "mini"), 64) for n in ("mini", "mini_tiny", "mini_relu")] + [(full, str(tmp_path), 416)]
+    multi = 0
+    for cfg, where, size in cases:
+        net = build(cfg, where)
+        defs = net.module_defs
+        lay = analyse(defs, net.module_list, int(net.hyperparams["channels"]), size, size)
+        assert lay.shp == _reference_shapes(net, size), cfg
+        assert len(lay.users) == len(defs)
+        for r, (ctot, parts) in lay.concat.items():
+            src = [r + int(t) if int(t) < 0 else int(t) for t in defs[r]["layers"].split(",")]
+            assert [s for s, _, _ in parts] == src and len(src) > 1
+            off = 0
+            for s, o, wd in parts:                           # consecutive slices, each as wide as its padded source
+                assert o == off and wd == pad8(lay.shp[s][0])
+                off += wd
+            assert off == ctot and ctot >= lay.shp[r][0]
+            assert all(r in lay.users[s] for s in src)
+            multi += 1
+        for s, (r, o) in lay.dest.items():                   # an in-place producer owns exactly one of those slices
+            assert (s, o, pad8(lay.shp[s][0])) in lay.concat[r][1]
+            assert defs[s]["type"] in ("convolutional", "upsample", "shortcut", "maxpool")
+    assert multi >= 5                                        # 2 in yolo_baseline, at least one per mini cfg
+    # the two guards, on cfgs derived from mini.cfg's header
+    head = open(os.path.join(G, "mini", "mini.cfg")).read().split("[convolutional]")[0]
+
+    def conv(f, k):
+        return f"[convolutional]\nfilters={f}\nsize={k}\nstride=1\n\n"
+    bad_route = head + conv(12, 3) + conv(16, 3) + "[route]\nlayers=-2, -1\n\n" + conv("preyolo", 1) + "[yolo]\n"
+    bad_pool = head + conv(16, 3) + "[maxpool]\nsize=17\nstride=1\n\n" + conv("preyolo", 1) + "[yolo]\n"
+    for text, msg in ((bad_route, r"\[route\] at section 2: source 0 has 12 channels; every concat source but the last must have a multiple of 8 channels"),
+                      (bad_pool, "max-pool windows up to 15x15 are lowered")):
+        cfg = tmp_path / "bad.cfg"
+        cfg.write_text(text)
+        net = build(str(cfg), os.path.join(G, "mini"))       # (dataset/train.csv is looked up relative to the working directory)
+        with pytest.raises(NotImplementedError, match=msg):
+            analyse(net.module_defs, net.module_list, 3, 64, 64)
