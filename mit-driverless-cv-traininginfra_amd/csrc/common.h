@@ -119,7 +119,7 @@ __device__ __forceinline__ uint4 mdcv_ld_stream(const void* p) {
 }
 
 // BatchNorm(+activation)-backward apply of ONE element: dy = cA * g + cB * y + cC with g = dz * act'(scale * y + shift).  Explicit fused
-// multiply-adds in a fixed order: the apply pass (elementwise.hip) and the kernels that form dy in their operand load (wgrad_gemm.hip BNA)
+// multiply-adds in a fixed order: the apply pass (bn_bwd.hip) and the kernels that form dy in their operand load (wgrad_gemm.hip BNA)
 // must round identically -- left to -ffp-contract, two kernels contract the same expression differently and differ in the last fp32 bit.
 __device__ __forceinline__ float mdcv_bn_bwd_dy(float dz, float y, float scale, float shift, float cA, float cB, float cC, int act, float slope) {
   const float pre = __builtin_fmaf(y, scale, shift);

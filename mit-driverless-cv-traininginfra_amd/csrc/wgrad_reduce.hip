@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kk_kernel(const float* __res
     for (int sp = q; sp < splits; sp += 4) {
       const float* ps = p + (size_t)sp * slab;
 #pragma unroll
-      for (int t = 0; t < KK; ++t) acc[t] += __builtin_nontemporal_load(ps + t * Cin_pad);   // the slabs' only reader (elementwise.hip: ld_stream; 13.11 / 13.09 -> 13.05 / 13.07 ms)
+      for (int t = 0; t < KK; ++t) acc[t] += __builtin_nontemporal_load(ps + t * Cin_pad);   // the slabs' only reader (strip.h: ld_stream; 13.11 / 13.09 -> 13.05 / 13.07 ms)
     }
   }
 #pragma unroll

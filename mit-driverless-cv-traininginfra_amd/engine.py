@@ -715,7 +715,7 @@ class Plan:
                                        # class and cost 100 us against 20-28 us for the stand-alone pass (same-box A/B, scripts/ab_step.py "F13;F141": -0.07 ms per step)
     # Data gradients whose fused sums would take more than this many partial rows (RektNet's 80^2 x 256 tensors: 12 800; YOLOv3's 208^2 / 416^2
     # layers) keep the stand-alone reduce pass.  The finalize can take them since round 2 (rows beyond 4096 are folded in place first,
-    # csrc/elementwise.hip), but the fused store loops still lose on these HBM-bound layers: RektNet 31.99k -> 31.34k img/s, YOLOv3 2136 -> 2118
+    # csrc/col_reduce.hip), but the fused store loops still lose on these HBM-bound layers: RektNet 31.99k -> 31.34k img/s, YOLOv3 2136 -> 2118
     # with the limit lifted (same-box A/B).
     fuse_max_rows = 4096
     fuse_max_rows_s2 = 1 << 16          # the stride-2 shift form (see _fuse_bn_sums); rows beyond 4096 are folded in place by the finalize

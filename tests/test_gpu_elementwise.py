@@ -1,4 +1,4 @@
-"""-m gpu: the BatchNorm / per-channel kernels of csrc/elementwise.hip and the optimizers of csrc/optim.hip at production
+"""-m gpu: the BatchNorm / per-channel kernels of csrc/bn_fwd.hip, bn_bwd.hip and col_reduce.hip and the optimizers of csrc/optim.hip at production
 sizes, through the C ABI, against float64 references computed on the CPU from the values AS STORED on the device.
 
 Groups (the numbers are those of the sections below):
@@ -36,7 +36,7 @@ trip of the unrolled loop = 4 PPI pixels.  wg = workgroups; "live a/4" = pixels 
 or 24 channels into its buffer; the others are contiguous (ld = C), as the plans pass most tensors.  The dual rows run the two-BatchNorm
 form (y2), the others the single one.  The reduce row counts the table quotes are asserted from mdcv_bn_act_bwd_reduce_ws_floats.
 The forward / apply workgroup counts and the "live a/4" figures have no public query: they are computed by hand from make_strip(M, C, 2048, 4)
-and make_strip(M, C, 1024, 8) in csrc/elementwise.hip as of this commit; a change of the strip heuristics needs the table redone.
+and make_strip(M, C, kReduceBlocks = 1024, 8) in csrc/strip.h as of this commit; a change of the strip heuristics needs the table redone.
 mdcv_bn_act_bwd_reduce_finalize's column stage only ever sees the reduce kernel's own rows (at most 1024); test_reduce_finalize_row_counts
 drives it at 1, 63, 64 and 65 rows, the fold tests of section 4 drive the other two entry points up to 20 001 rows.
 
