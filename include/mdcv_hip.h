@@ -306,6 +306,26 @@ int mdcv_imgload_aug_batch(const int* desc_host, const int* desc, const int* aug
                            const unsigned char* src, long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace,
                            void* aug_workspace, float* out, void* stream);
 
+/* ---- real key-point crop batches (csrc/kptload.hip; RektNet/dataset.py:34-56 ConeDataset.__getitem__ over RektNet/utils.py:73-96):
+ *      B decoded crops (uint8, HWC, RGB, any height and width, packed back to back in `src` at unaligned byte offsets) ->
+ *       images   [B,3,S,S] fp32: cv2.resize of the 8-bit crop to S x S with mdcv_crop_resize_u8's rule, then (float)(u8 / 255.0); the
+ *                planes are B, G, R (cv2.imread's order, which the reference keeps)
+ *       heatmaps [B,7,S,S] fp32: prep_label in float64 as mdcv_synth_crop_batch computes it (one-hot at the hot pixel of the original
+ *                crop -> INTER_LINEAR resize -> [1,4,6,4,1]/16 blur with BORDER_REFLECT_101 -> divided by sum_y * sum_x); a map whose
+ *                down-scaled one-hot misses every tap is all NaN (0 / 0), as in the reference
+ *      One descriptor of MDCV_KPTLOAD_DESC ints per crop (mdcv/data/crops.py writes them):
+ *       [0] src_off  byte offset of the crop in `src` (rows of w * 3 bytes)   [1] h   [2] w   [3] must be 0
+ *       [4 + 2k], [5 + 2k]  the hot pixel (int(x), int(y)) of key point k = 0..6, inside the crop   [18], [19] must be 0
+ *      Bounds, checked before the launch (MDCV_EARG, nothing is enqueued): MDCV_KPTLOAD_MIN_SIZE <= S <= MDCV_KPTLOAD_MAX_SIZE,
+ *      1 <= h, w <= MDCV_KPTLOAD_MAX_SIDE, every crop inside src_bytes <= 2^31 - 1, 1 <= B <= 65535.  desc_host is what is validated;
+ *      desc is its device copy, whose crop extents the kernel checks again (a crop that fails is written as zeros).  One launch. */
+#define MDCV_KPTLOAD_DESC 20
+#define MDCV_KPTLOAD_MIN_SIZE 16
+#define MDCV_KPTLOAD_MAX_SIZE 256
+#define MDCV_KPTLOAD_MAX_SIDE 4096
+int mdcv_kptload_batch(const int* desc_host, const int* desc, int B, const unsigned char* src, long long src_bytes, int S, float* images,
+                       float* heatmaps, void* stream);
+
 /* ---- optimizer step over the flat fp32 parameter buffer (train.py:180-187,72 ; train_eval.py:263,72) */
 int mdcv_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr, float beta1,
                    float beta2, float eps, float weight_decay, float grad_scale, void* stream);

@@ -5,6 +5,7 @@
 // vertical blend.  Box coordinates go back to frame pixels like CVC-YOLOv3/detect.py:98-101 (x * scale + offset).
 // Built with -ffp-contract=off so that the blends round like the oracle (two products, one sum).
 #include "common.h"
+#include "resize_u8.h"
 
 #define MDCV_CROP_MAX_SIDE 256
 
@@ -80,21 +81,6 @@ struct CropU8Args {
   float* out; int* owner; int* total;
 };
 
-__device__ __forceinline__ void make_tap_u8(int d, int dst, int src, bool clamp_weights, int& i0, int& i1, int& c0, int& c1) {
-  const double sc = 1.0 / ((double)dst / (double)src);
-  float f = (float)(((double)d + 0.5) * sc - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (clamp_weights) {
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= src - 1) { s = src - 1; f = 0.f; }
-  }
-  c0 = (int)rintf((1.f - f) * 2048.f);
-  c1 = (int)rintf(f * 2048.f);
-  i0 = s < 0 ? 0 : (s < src ? s : src - 1);
-  i1 = s + 1 < 0 ? 0 : (s + 1 < src ? s + 1 : src - 1);
-}
-
 __global__ __launch_bounds__(256) void crop_resize_u8_kernel(CropU8Args A) {
   __shared__ int x0[MDCV_CROP_MAX_SIDE], x1[MDCV_CROP_MAX_SIDE], y0[MDCV_CROP_MAX_SIDE], y1[MDCV_CROP_MAX_SIDE];
   __shared__ int a0s[MDCV_CROP_MAX_SIDE], a1s[MDCV_CROP_MAX_SIDE], b0s[MDCV_CROP_MAX_SIDE], b1s[MDCV_CROP_MAX_SIDE];
@@ -124,8 +110,7 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(CropU8Args A) {
       const unsigned char* r1 = src + (size_t)y1[y] * A.W;
       const int d0 = (int)r0[x0[x]] * a0s[x] + (int)r0[x1[x]] * a1s[x];
       const int d1 = (int)r1[x0[x]] * a0s[x] + (int)r1[x1[x]] * a1s[x];
-      const int v = (((b0s[y] * (d0 >> 4)) >> 16) + ((b1s[y] * (d1 >> 4)) >> 16) + 2) >> 2;
-      o[(size_t)c * plane + i] = (float)((double)(unsigned char)v / 255.0);
+      o[(size_t)c * plane + i] = blend_rows_u8(b0s[y], d0, b1s[y], d1);
     }
   }
 }

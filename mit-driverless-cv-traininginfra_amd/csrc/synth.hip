@@ -4,6 +4,7 @@
 // Every value is a pure function of (seed, step, index) through a counter-based integer hash, so the numpy oracle
 // (oracle/synth_oracle.py) reproduces the tensors bit for bit; built with -ffp-contract=off for that reason.
 #include "common.h"
+#include "kpt_heatmap.h"
 
 namespace {
 
@@ -73,22 +74,10 @@ __global__ __launch_bounds__(256) void synth_images_kernel(unsigned seed, int st
 }
 
 // ---- key-point data: one workgroup per crop
-__device__ __forceinline__ double resize_onehot(int d, int hot, int src, int dst) {   // cv2 INTER_LINEAR sample d of a one-hot at `hot`
-  const double sc = (double)src / (double)dst;
-  float fx = (float)(((double)d + 0.5) * sc - 0.5);
-  int sx = (int)floorf(fx);
-  fx = fx - (float)sx;
-  if (sx < 0) { sx = 0; fx = 0.f; }
-  if (sx >= src - 1) { sx = src - 1; fx = 0.f; }
-  const int s1 = sx + 1 < src ? sx + 1 : src - 1;
-  const double f = (double)fx;
-  return (1.0 - f) * (sx == hot ? 1.0 : 0.0) + f * (s1 == hot ? 1.0 : 0.0);
-}
-
 template <int S>
 __global__ __launch_bounds__(256) void synth_crops_kernel(unsigned seed, int step, int B, float* __restrict__ img, float* __restrict__ hm,
                                                           float* __restrict__ pts) {
-  __shared__ double rz[2][7][S], bl[2][7][S], tot[7];
+  __shared__ double rz[2 * 7 * S], bl[2 * 7 * S], sums[2 * 7];
   __shared__ int hot[7][2];
   const int b = blockIdx.x, tid = threadIdx.x;
   const unsigned long long key = (unsigned long long)step * 4099ull + (unsigned long long)b;
@@ -123,37 +112,9 @@ __global__ __launch_bounds__(256) void synth_crops_kernel(unsigned seed, int ste
     pts[((size_t)b * 7 + tid) * 2 + 1] = (float)(ceil((double)iy * hs) / (double)S);
   }
   __syncthreads();
-  // heat-maps (RektNet/utils.py:83-97): resized one-hot and 5-tap blur are separable -> two vectors per key point
-  for (int i = tid; i < 2 * 7 * S; i += 256) {
-    const int a = i / (7 * S), r = i - a * 7 * S, k = r / S, d = r - k * S;     // a = 0: x axis, 1: y axis
-    rz[a][k][d] = resize_onehot(d, hot[k][a], a == 0 ? ow : oh, S);
-  }
-  __syncthreads();
-  for (int i = tid; i < 2 * 7 * S; i += 256) {
-    const int a = i / (7 * S), r = i - a * 7 * S, k = r / S, d = r - k * S;
-    const double g[5] = {1.0 / 16.0, 4.0 / 16.0, 6.0 / 16.0, 4.0 / 16.0, 1.0 / 16.0};
-    double acc = 0.0;
-#pragma unroll
-    for (int t = -2; t <= 2; ++t) {
-      int j = d + t;
-      if (j < 0) j = -j;
-      if (j >= S) j = 2 * (S - 1) - j;                                          // BORDER_REFLECT_101
-      acc += g[t + 2] * rz[a][k][j];
-    }
-    bl[a][k][d] = acc;
-  }
-  __syncthreads();
-  if (tid < 7) {
-    double sy = 0.0, sx = 0.0;
-    for (int d = 0; d < S; ++d) sy += bl[1][tid][d];
-    for (int d = 0; d < S; ++d) sx += bl[0][tid][d];
-    tot[tid] = sy * sx;
-  }
-  __syncthreads();
-  for (int i = tid; i < 7 * S * S; i += 256) {
-    const int k = i / (S * S), r = i - k * S * S, y = r / S, x = r - y * S;
-    hm[(size_t)b * 7 * S * S + i] = (float)((bl[1][k][y] * bl[0][k][x]) / tot[k]);
-  }
+  // heat-maps (RektNet/utils.py:83-97): resized one-hot and 5-tap blur are separable -> two vectors per key point (kpt_heatmap.h)
+  kpthm::axes(rz, bl, sums, &hot[0][0], 7, ow, oh, S, tid, 256);
+  kpthm::store(hm + (size_t)b * 7 * S * S, bl, sums, 7, S, tid, 256, S % 4 == 0 && ((uintptr_t)hm & 15) == 0);
 }
 
 }  // namespace

@@ -1,3 +1,4 @@
-"""Detector and key-point batches on the GPU: synthetic cones, and real images with the reference's dataset contract."""
+"""Detector and key-point batches on the GPU: synthetic cones, and real images and real cone crops with the reference's dataset contracts."""
 from .synth import SyntheticCones, SyntheticConeCrops  # noqa: F401
 from .images import ImageLabelBatches  # noqa: F401
+from .crops import ConeCropBatches, load_train_csv_dataset  # noqa: F401
