@@ -306,6 +306,27 @@ int mdcv_imgload_aug_batch(const int* desc_host, const int* desc, const int* aug
                            const unsigned char* src, long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace,
                            void* aug_workspace, float* out, void* stream);
 
+/* ---- the same two batches with source windows referenced in place in a device-resident frame cache (mdcv/data/framecache.py).  Per image
+ *      the horizontal pass reads EITHER its staged window in `src` (as above) OR a rectangle of a decoded frame kept in `pool`.  The choice
+ *      is one row of MDCV_IMGLOAD_FREF long longs per image, beside the descriptors (fref_host / fref: host and device copy):
+ *       [0] off     byte offset of the frame in `pool`, or -1: this image is staged and descriptor word [0] locates it (the other three
+ *                   words are then not read)
+ *       [1] pitch   bytes from one frame row to the next (3 * frame width; any value, no alignment is assumed)
+ *       [2] x0  [3] y0   the window's origin in the frame:  pixel(wy, x) = pool[off + (y0 + wy) * pitch + 3 * (x0 + x)]
+ *      A reference is good when off, x0, y0 >= 0, pitch >= 3 * (x0 + win_w) and off + (y0 + win_h - 1) * pitch + 3 * (x0 + win_w)
+ *      <= pool_bytes (64-bit arithmetic; empty windows allowed).  A pooled image's descriptor word [0] is not read; everything else of
+ *      the descriptor, the tables, the scratch and the launches are those of the staged entry points, and the bytes written are the same.
+ *      fref_host is validated with desc_host (MDCV_EARG, nothing is enqueued); the kernels check the device copies again (an image that
+ *      fails is written as zeros).  pool_bytes <= 2^60; pool may be NULL when pool_bytes is 0. */
+#define MDCV_IMGLOAD_FREF 4
+int mdcv_imgload_frames_batch(const int* desc_host, const int* desc, const long long* fref_host, const long long* fref, int B, const int* coefs,
+                              long long n_coefs, const unsigned char* src, long long src_bytes, const unsigned char* pool, long long pool_bytes,
+                              int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace, float* out, void* stream);
+int mdcv_imgload_aug_frames_batch(const int* desc_host, const int* desc, const long long* fref_host, const long long* fref, const int* aug_host,
+                                  const int* aug, int B, const int* coefs, long long n_coefs, const unsigned char* src, long long src_bytes,
+                                  const unsigned char* pool, long long pool_bytes, int max_scr_w, int max_scr_h, int C, int H, int W,
+                                  void* workspace, void* aug_workspace, float* out, void* stream);
+
 /* ---- real key-point crop batches (csrc/kptload.hip; RektNet/dataset.py:34-56 ConeDataset.__getitem__ over RektNet/utils.py:73-96):
  *      B decoded crops (uint8, HWC, RGB, any height and width, packed back to back in `src` at unaligned byte offsets) ->
  *       images   [B,3,S,S] fp32: cv2.resize of the 8-bit crop to S x S with mdcv_crop_resize_u8's rule, then (float)(u8 / 255.0); the

@@ -124,16 +124,18 @@ __device__ inline Rgb jitter_chain(Rgb p, const int* a, int mean) {
 __device__ __forceinline__ Rgb unpack(unsigned v) { return Rgb{(int)(v & 255u), (int)((v >> 8) & 255u), (int)((v >> 16) & 255u)}; }
 
 // The uint8 patch: imgload_vpass_kernel's pixel without hflip / convert('L') / /255, as [B][H][W] RGBX.  Also clears the luma sums.
-__global__ __launch_bounds__(256) void imgaug_patch_u8_kernel(const int* __restrict__ desc, const int* __restrict__ coefs, long long n_coefs,
-                                                              long long src_bytes, int max_scr_w, int max_scr_h, int H, int W,
+__global__ __launch_bounds__(256) void imgaug_patch_u8_kernel(const int* __restrict__ desc, const long long* __restrict__ fref,
+                                                              const int* __restrict__ coefs, long long n_coefs, long long src_bytes,
+                                                              long long pool_bytes, int max_scr_w, int max_scr_h, int H, int W,
                                                               const unsigned char* __restrict__ ws, unsigned* __restrict__ patch,
                                                               unsigned* __restrict__ sums) {
   __shared__ int sdesc[MDCV_IMGLOAD_DESC];
+  __shared__ long long sfref[MDCV_IMGLOAD_FREF];
   const int b = blockIdx.z, tid = threadIdx.x;
-  if (tid < MDCV_IMGLOAD_DESC) sdesc[tid] = desc[(size_t)b * MDCV_IMGLOAD_DESC + tid];
+  const long long* f = imgload_stage_desc(sdesc, sfref, desc, fref, b, tid);
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) sums[b] = 0u;
   __syncthreads();
-  const bool ok = desc_ok(sdesc, n_coefs, src_bytes, max_scr_w, max_scr_h);
+  const bool ok = image_ok(sdesc, f, n_coefs, src_bytes, pool_bytes, max_scr_w, max_scr_h);
   const int x = blockIdx.x * 64 + (tid & 63);
   if (x >= W) return;
   unsigned* pb = patch + (size_t)b * H * W;
@@ -170,17 +172,19 @@ __global__ __launch_bounds__(256) void imgaug_jitter_stats_kernel(const int* __r
 // Per output pixel: the inverse affine map in double, four clamped taps each through the jitter chain, the bilinear blend, then exactly
 // what imgload_vpass_kernel does behind its pixel: convert('L'), mirrored store, /255 into [B,C,H,W] fp32.  An image with neither jitter
 // nor affine is copied (the same bytes as the two-launch path); an image whose descriptor fails the check is written as zeros.
-__global__ __launch_bounds__(256) void imgaug_apply_kernel(const int* __restrict__ desc, const int* __restrict__ aug, long long n_coefs,
-                                                           long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W,
+__global__ __launch_bounds__(256) void imgaug_apply_kernel(const int* __restrict__ desc, const long long* __restrict__ fref,
+                                                           const int* __restrict__ aug, long long n_coefs, long long src_bytes,
+                                                           long long pool_bytes, int max_scr_w, int max_scr_h, int C, int H, int W,
                                                            const unsigned* __restrict__ patch, const unsigned* __restrict__ sums,
                                                            float* __restrict__ out) {
   __shared__ int sa[MDCV_IMGAUG_DESC];
   __shared__ int sdesc[MDCV_IMGLOAD_DESC];
+  __shared__ long long sfref[MDCV_IMGLOAD_FREF];
   const int b = blockIdx.z, tid = threadIdx.x;
-  if (tid < MDCV_IMGAUG_DESC) sa[tid] = aug[(size_t)b * MDCV_IMGAUG_DESC + tid];
-  if (tid >= 64 && tid < 64 + MDCV_IMGLOAD_DESC) sdesc[tid - 64] = desc[(size_t)b * MDCV_IMGLOAD_DESC + tid - 64];
+  if (tid >= 64 && tid < 64 + MDCV_IMGAUG_DESC) sa[tid - 64] = aug[(size_t)b * MDCV_IMGAUG_DESC + tid - 64];
+  const long long* f = imgload_stage_desc(sdesc, sfref, desc, fref, b, tid);
   __syncthreads();
-  const bool ok = aug_ok(sa) && desc_ok(sdesc, n_coefs, src_bytes, max_scr_w, max_scr_h);
+  const bool ok = aug_ok(sa) && image_ok(sdesc, f, n_coefs, src_bytes, pool_bytes, max_scr_w, max_scr_h);
   const int ox = blockIdx.x * 64 + (tid & 63);
   if (ox >= W) return;
   const int x = ok && sdesc[D_FLIP] ? W - 1 - ox : ox;
@@ -234,6 +238,45 @@ __global__ __launch_bounds__(256) void imgaug_apply_kernel(const int* __restrict
 
 inline long long patch_bytes(int B, int H, int W) { return ((long long)B * H * W * 4 + 255) / 256 * 256; }
 
+// Both entry points: fref_host == fref == nullptr is the staged form.
+int imgaug_batch_impl(const int* desc_host, const int* desc, const long long* fref_host, const long long* fref, const int* aug_host,
+                      const int* aug, int B, const int* coefs, long long n_coefs, const unsigned char* src, long long src_bytes,
+                      const unsigned char* pool, long long pool_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace,
+                      void* aug_workspace, float* out, void* stream) {
+  if (!desc_host || !desc || !aug_host || !aug || !coefs || !out || !aug_workspace) return MDCV_EARG;
+  if (B <= 0 || B > 65535 || n_coefs <= 0 || src_bytes < 0 || (src_bytes > 0 && !src)) return MDCV_EARG;
+  if (pool_bytes < 0 || pool_bytes > IMGLOAD_MAX_POOL || (pool_bytes > 0 && !pool)) return MDCV_EARG;
+  if (max_scr_w < 0 || max_scr_h < 0 || (!workspace && (long long)max_scr_w * max_scr_h > 0)) return MDCV_EARG;
+  if ((C != 1 && C != 3) || H <= 0 || W <= 0 || (long long)H * W > IMGAUG_MAX_PIXELS) return MDCV_EARG;
+  bool any_jitter = false;
+  for (int b = 0; b < B; ++b) {
+    if (!image_ok(desc_host + (size_t)b * MDCV_IMGLOAD_DESC, fref_host ? fref_host + (size_t)b * MDCV_IMGLOAD_FREF : nullptr, n_coefs,
+                  src_bytes, pool_bytes, max_scr_w, max_scr_h))
+      return MDCV_EARG;
+    if (!aug_ok(aug_host + (size_t)b * MDCV_IMGAUG_DESC)) return MDCV_EARG;
+    any_jitter = any_jitter || aug_host[(size_t)b * MDCV_IMGAUG_DESC + A_JITTER] != 0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* patch = (unsigned*)aug_workspace;
+  unsigned* sums = (unsigned*)((char*)aug_workspace + patch_bytes(B, H, W));
+  if ((long long)max_scr_w * max_scr_h > 0) {
+    const int rc = imgload_launch_hpass(desc, fref, B, coefs, n_coefs, src, src_bytes, pool, pool_bytes, max_scr_w, max_scr_h, workspace, stream);
+    if (rc != MDCV_OK) return rc;
+  }
+  const dim3 grid((unsigned)(W + 63) / 64, (unsigned)(H + 3) / 4 < 64u ? (unsigned)(H + 3) / 4 : 64u, (unsigned)B);
+  MDCV_LAUNCH(imgaug_patch_u8_kernel, grid, dim3(256), 0, st, desc, fref, coefs, n_coefs, src_bytes, pool_bytes, max_scr_w, max_scr_h, H, W,
+              (const unsigned char*)workspace, patch, sums);
+  MDCV_CHECK_LAUNCH();
+  if (any_jitter) {
+    MDCV_LAUNCH(imgaug_jitter_stats_kernel, grid, dim3(256), 0, st, aug, H, W, (const unsigned*)patch, sums);
+    MDCV_CHECK_LAUNCH();
+  }
+  MDCV_LAUNCH(imgaug_apply_kernel, grid, dim3(256), 0, st, desc, fref, aug, n_coefs, src_bytes, pool_bytes, max_scr_w, max_scr_h, C, H, W,
+              (const unsigned*)patch, (const unsigned*)sums, out);
+  MDCV_CHECK_LAUNCH();
+  return MDCV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -246,35 +289,17 @@ long long mdcv_imgaug_workspace_bytes(int B, int H, int W) {
 int mdcv_imgload_aug_batch(const int* desc_host, const int* desc, const int* aug_host, const int* aug, int B, const int* coefs, long long n_coefs,
                            const unsigned char* src, long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace,
                            void* aug_workspace, float* out, void* stream) {
-  if (!desc_host || !desc || !aug_host || !aug || !coefs || !out || !aug_workspace) return MDCV_EARG;
-  if (B <= 0 || B > 65535 || n_coefs <= 0 || src_bytes < 0 || (src_bytes > 0 && !src)) return MDCV_EARG;
-  if (max_scr_w < 0 || max_scr_h < 0 || (!workspace && (long long)max_scr_w * max_scr_h > 0)) return MDCV_EARG;
-  if ((C != 1 && C != 3) || H <= 0 || W <= 0 || (long long)H * W > IMGAUG_MAX_PIXELS) return MDCV_EARG;
-  bool any_jitter = false;
-  for (int b = 0; b < B; ++b) {
-    if (!desc_ok(desc_host + (size_t)b * MDCV_IMGLOAD_DESC, n_coefs, src_bytes, max_scr_w, max_scr_h)) return MDCV_EARG;
-    if (!aug_ok(aug_host + (size_t)b * MDCV_IMGAUG_DESC)) return MDCV_EARG;
-    any_jitter = any_jitter || aug_host[(size_t)b * MDCV_IMGAUG_DESC + A_JITTER] != 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  unsigned* patch = (unsigned*)aug_workspace;
-  unsigned* sums = (unsigned*)((char*)aug_workspace + patch_bytes(B, H, W));
-  if ((long long)max_scr_w * max_scr_h > 0) {
-    const int rc = imgload_launch_hpass(desc, B, coefs, n_coefs, src, src_bytes, max_scr_w, max_scr_h, workspace, stream);
-    if (rc != MDCV_OK) return rc;
-  }
-  const dim3 grid((unsigned)(W + 63) / 64, (unsigned)(H + 3) / 4 < 64u ? (unsigned)(H + 3) / 4 : 64u, (unsigned)B);
-  MDCV_LAUNCH(imgaug_patch_u8_kernel, grid, dim3(256), 0, st, desc, coefs, n_coefs, src_bytes, max_scr_w, max_scr_h, H, W,
-              (const unsigned char*)workspace, patch, sums);
-  MDCV_CHECK_LAUNCH();
-  if (any_jitter) {
-    MDCV_LAUNCH(imgaug_jitter_stats_kernel, grid, dim3(256), 0, st, aug, H, W, (const unsigned*)patch, sums);
-    MDCV_CHECK_LAUNCH();
-  }
-  MDCV_LAUNCH(imgaug_apply_kernel, grid, dim3(256), 0, st, desc, aug, n_coefs, src_bytes, max_scr_w, max_scr_h, C, H, W,
-              (const unsigned*)patch, (const unsigned*)sums, out);
-  MDCV_CHECK_LAUNCH();
-  return MDCV_OK;
+  return imgaug_batch_impl(desc_host, desc, nullptr, nullptr, aug_host, aug, B, coefs, n_coefs, src, src_bytes, nullptr, 0, max_scr_w,
+                           max_scr_h, C, H, W, workspace, aug_workspace, out, stream);
+}
+
+int mdcv_imgload_aug_frames_batch(const int* desc_host, const int* desc, const long long* fref_host, const long long* fref, const int* aug_host,
+                                  const int* aug, int B, const int* coefs, long long n_coefs, const unsigned char* src, long long src_bytes,
+                                  const unsigned char* pool, long long pool_bytes, int max_scr_w, int max_scr_h, int C, int H, int W,
+                                  void* workspace, void* aug_workspace, float* out, void* stream) {
+  if (!fref_host || !fref) return MDCV_EARG;
+  return imgaug_batch_impl(desc_host, desc, fref_host, fref, aug_host, aug, B, coefs, n_coefs, src, src_bytes, pool, pool_bytes, max_scr_w,
+                           max_scr_h, C, H, W, workspace, aug_workspace, out, stream);
 }
 
 }  // extern "C"

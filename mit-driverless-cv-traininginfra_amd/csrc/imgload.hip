@@ -12,14 +12,19 @@ namespace {
 
 // Horizontal pass: scratch[b][i][j] = resize of window row (row0 + i) at resized column j; rows outside the window are the 127 canvas.
 // 64 columns x 4 rows per workgroup, rows grid-strided; a lane keeps its column's table entry for all of its rows.
-__global__ __launch_bounds__(256) void imgload_hpass_kernel(const int* __restrict__ desc, const int* __restrict__ coefs, long long n_coefs,
-                                                            const unsigned char* __restrict__ src, long long src_bytes, int max_scr_w,
+// The window's bytes are either staged (packed rows of 3 * win_w at src + src_off) or a rectangle of a cached frame in `pool`, named by
+// the image's row of `fref`; only the base pointer and the row pitch differ, the taps and the canvas are the same.
+__global__ __launch_bounds__(256) void imgload_hpass_kernel(const int* __restrict__ desc, const long long* __restrict__ fref,
+                                                            const int* __restrict__ coefs, long long n_coefs,
+                                                            const unsigned char* __restrict__ src, long long src_bytes,
+                                                            const unsigned char* __restrict__ pool, long long pool_bytes, int max_scr_w,
                                                             int max_scr_h, unsigned char* __restrict__ ws) {
   __shared__ int sdesc[MDCV_IMGLOAD_DESC];
+  __shared__ long long sfref[MDCV_IMGLOAD_FREF];
   const int b = blockIdx.z, tid = threadIdx.x;
-  if (tid < MDCV_IMGLOAD_DESC) sdesc[tid] = desc[(size_t)b * MDCV_IMGLOAD_DESC + tid];
+  const long long* f = imgload_stage_desc(sdesc, sfref, desc, fref, b, tid);
   __syncthreads();
-  if (!desc_ok(sdesc, n_coefs, src_bytes, max_scr_w, max_scr_h)) return;
+  if (!image_ok(sdesc, f, n_coefs, src_bytes, pool_bytes, max_scr_w, max_scr_h)) return;
   const int scr_w = sdesc[D_SCR_W], scr_h = sdesc[D_SCR_H];
   const int j = blockIdx.x * 64 + (tid & 63);
   if (blockIdx.x * 64 >= scr_w) return;                        // whole workgroup past this image's columns
@@ -27,13 +32,15 @@ __global__ __launch_bounds__(256) void imgload_hpass_kernel(const int* __restric
   const int* e = coefs + sdesc[D_CX_OFF] + (size_t)(j < scr_w ? j : scr_w - 1) * (ks + 2);
   const int x0 = e[0];
   const int cnt = e[1] < ks ? e[1] : ks;
-  const unsigned char* s = src + sdesc[D_SRC_OFF];
+  const bool pooled = f && f[F_OFF] != -1;
+  const size_t pitch = pooled ? (size_t)f[F_PITCH] : (size_t)win_w * 3;
+  const unsigned char* s = pooled ? pool + f[F_OFF] + (size_t)f[F_Y0] * pitch + 3 * (size_t)f[F_X0] : src + sdesc[D_SRC_OFF];
   unsigned char* o = ws + (size_t)b * max_scr_w * max_scr_h * 3;
   if (j >= scr_w) return;
   for (int i = blockIdx.y * 4 + (tid >> 6); i < scr_h; i += gridDim.y * 4) {
     const int wy = row0 + i;
     const bool row_in = wy >= 0 && wy < win_h;
-    const unsigned char* r = s + (size_t)(row_in ? wy : 0) * win_w * 3;
+    const unsigned char* r = s + (size_t)(row_in ? wy : 0) * pitch;
     int a0 = 1 << (IMGLOAD_PREC - 1), a1 = a0, a2 = a0;
     for (int t = 0; t < cnt; ++t) {
       const int x = x0 + t;
@@ -48,14 +55,16 @@ __global__ __launch_bounds__(256) void imgload_hpass_kernel(const int* __restric
 }
 
 // Vertical pass and everything after it: resize along y from the scratch, 127 padding / 0 outside, convert('L'), hflip, /255, NCHW fp32.
-__global__ __launch_bounds__(256) void imgload_vpass_kernel(const int* __restrict__ desc, const int* __restrict__ coefs, long long n_coefs,
-                                                            long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W,
+__global__ __launch_bounds__(256) void imgload_vpass_kernel(const int* __restrict__ desc, const long long* __restrict__ fref,
+                                                            const int* __restrict__ coefs, long long n_coefs, long long src_bytes,
+                                                            long long pool_bytes, int max_scr_w, int max_scr_h, int C, int H, int W,
                                                             const unsigned char* __restrict__ ws, float* __restrict__ out) {
   __shared__ int sdesc[MDCV_IMGLOAD_DESC];
+  __shared__ long long sfref[MDCV_IMGLOAD_FREF];
   const int b = blockIdx.z, tid = threadIdx.x;
-  if (tid < MDCV_IMGLOAD_DESC) sdesc[tid] = desc[(size_t)b * MDCV_IMGLOAD_DESC + tid];
+  const long long* f = imgload_stage_desc(sdesc, sfref, desc, fref, b, tid);
   __syncthreads();
-  const bool ok = desc_ok(sdesc, n_coefs, src_bytes, max_scr_w, max_scr_h);
+  const bool ok = image_ok(sdesc, f, n_coefs, src_bytes, pool_bytes, max_scr_w, max_scr_h);
   const int ox = blockIdx.x * 64 + (tid & 63);
   if (ox >= W) return;
   const size_t plane = (size_t)H * W;
@@ -76,15 +85,46 @@ __global__ __launch_bounds__(256) void imgload_vpass_kernel(const int* __restric
 
 }  // namespace
 
-int imgload_launch_hpass(const int* desc, int B, const int* coefs, long long n_coefs, const unsigned char* src, long long src_bytes,
-                         int max_scr_w, int max_scr_h, void* workspace, void* stream) {
+int imgload_launch_hpass(const int* desc, const long long* fref, int B, const int* coefs, long long n_coefs, const unsigned char* src,
+                         long long src_bytes, const unsigned char* pool, long long pool_bytes, int max_scr_w, int max_scr_h, void* workspace,
+                         void* stream) {
   const unsigned char* s = src ? src : reinterpret_cast<const unsigned char*>(coefs);      // no window bytes at all: every read is the canvas
+  const unsigned char* q = pool ? pool : s;                                                 // no pool: no reference passes with pool_bytes 0
   const unsigned gy = (unsigned)(max_scr_h + 3) / 4 < 64u ? (unsigned)(max_scr_h + 3) / 4 : 64u;
-  MDCV_LAUNCH(imgload_hpass_kernel, dim3((unsigned)(max_scr_w + 63) / 64, gy, (unsigned)B), dim3(256), 0, (hipStream_t)stream, desc, coefs,
-              n_coefs, s, src_bytes, max_scr_w, max_scr_h, (unsigned char*)workspace);
+  MDCV_LAUNCH(imgload_hpass_kernel, dim3((unsigned)(max_scr_w + 63) / 64, gy, (unsigned)B), dim3(256), 0, (hipStream_t)stream, desc, fref,
+              coefs, n_coefs, s, src_bytes, q, pool_bytes, max_scr_w, max_scr_h, (unsigned char*)workspace);
   MDCV_CHECK_LAUNCH();
   return MDCV_OK;
 }
+
+namespace {
+
+// Both entry points: fref_host == fref == nullptr is the staged form.
+int imgload_batch_impl(const int* desc_host, const int* desc, const long long* fref_host, const long long* fref, int B, const int* coefs,
+                       long long n_coefs, const unsigned char* src, long long src_bytes, const unsigned char* pool, long long pool_bytes,
+                       int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace, float* out, void* stream) {
+  if (!desc_host || !desc || !coefs || !out || B <= 0 || B > 65535 || n_coefs <= 0 || src_bytes < 0 || (src_bytes > 0 && !src)) return MDCV_EARG;
+  if (pool_bytes < 0 || pool_bytes > IMGLOAD_MAX_POOL || (pool_bytes > 0 && !pool)) return MDCV_EARG;
+  if (max_scr_w < 0 || max_scr_h < 0 || (!workspace && (long long)max_scr_w * max_scr_h > 0)) return MDCV_EARG;
+  if ((C != 1 && C != 3) || H <= 0 || W <= 0) return MDCV_EARG;
+  for (int b = 0; b < B; ++b)
+    if (!image_ok(desc_host + (size_t)b * MDCV_IMGLOAD_DESC, fref_host ? fref_host + (size_t)b * MDCV_IMGLOAD_FREF : nullptr, n_coefs,
+                  src_bytes, pool_bytes, max_scr_w, max_scr_h))
+      return MDCV_EARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned char* ws = (const unsigned char*)workspace;
+  if ((long long)max_scr_w * max_scr_h > 0) {
+    const int rc = imgload_launch_hpass(desc, fref, B, coefs, n_coefs, src, src_bytes, pool, pool_bytes, max_scr_w, max_scr_h, workspace, stream);
+    if (rc != MDCV_OK) return rc;
+  }
+  const unsigned gy = (unsigned)(H + 3) / 4 < 64u ? (unsigned)(H + 3) / 4 : 64u;
+  MDCV_LAUNCH(imgload_vpass_kernel, dim3((unsigned)(W + 63) / 64, gy, (unsigned)B), dim3(256), 0, st, desc, fref, coefs, n_coefs, src_bytes,
+              pool_bytes, max_scr_w, max_scr_h, C, H, W, ws, out);
+  MDCV_CHECK_LAUNCH();
+  return MDCV_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -95,22 +135,16 @@ long long mdcv_imgload_workspace_bytes(int B, int max_scr_w, int max_scr_h) {
 
 int mdcv_imgload_batch(const int* desc_host, const int* desc, int B, const int* coefs, long long n_coefs, const unsigned char* src,
                        long long src_bytes, int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace, float* out, void* stream) {
-  if (!desc_host || !desc || !coefs || !out || B <= 0 || B > 65535 || n_coefs <= 0 || src_bytes < 0 || (src_bytes > 0 && !src)) return MDCV_EARG;
-  if (max_scr_w < 0 || max_scr_h < 0 || (!workspace && (long long)max_scr_w * max_scr_h > 0)) return MDCV_EARG;
-  if ((C != 1 && C != 3) || H <= 0 || W <= 0) return MDCV_EARG;
-  for (int b = 0; b < B; ++b)
-    if (!desc_ok(desc_host + (size_t)b * MDCV_IMGLOAD_DESC, n_coefs, src_bytes, max_scr_w, max_scr_h)) return MDCV_EARG;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned char* ws = (const unsigned char*)workspace;
-  if ((long long)max_scr_w * max_scr_h > 0) {
-    const int rc = imgload_launch_hpass(desc, B, coefs, n_coefs, src, src_bytes, max_scr_w, max_scr_h, workspace, stream);
-    if (rc != MDCV_OK) return rc;
-  }
-  const unsigned gy = (unsigned)(H + 3) / 4 < 64u ? (unsigned)(H + 3) / 4 : 64u;
-  MDCV_LAUNCH(imgload_vpass_kernel, dim3((unsigned)(W + 63) / 64, gy, (unsigned)B), dim3(256), 0, st, desc, coefs, n_coefs, src_bytes,
-              max_scr_w, max_scr_h, C, H, W, ws, out);
-  MDCV_CHECK_LAUNCH();
-  return MDCV_OK;
+  return imgload_batch_impl(desc_host, desc, nullptr, nullptr, B, coefs, n_coefs, src, src_bytes, nullptr, 0, max_scr_w, max_scr_h, C, H, W,
+                            workspace, out, stream);
+}
+
+int mdcv_imgload_frames_batch(const int* desc_host, const int* desc, const long long* fref_host, const long long* fref, int B, const int* coefs,
+                              long long n_coefs, const unsigned char* src, long long src_bytes, const unsigned char* pool, long long pool_bytes,
+                              int max_scr_w, int max_scr_h, int C, int H, int W, void* workspace, float* out, void* stream) {
+  if (!fref_host || !fref) return MDCV_EARG;
+  return imgload_batch_impl(desc_host, desc, fref_host, fref, B, coefs, n_coefs, src, src_bytes, pool, pool_bytes, max_scr_w, max_scr_h, C, H, W,
+                            workspace, out, stream);
 }
 
 }  // extern "C"

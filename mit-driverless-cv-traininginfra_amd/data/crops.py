@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import framecache
 
 DESC = 20                                # MDCV_KPTLOAD_DESC
 MIN_SIZE, MAX_SIZE, MAX_SIDE = 16, 256, 4096          # MDCV_KPTLOAD_MIN_SIZE / MAX_SIZE / MAX_SIDE
@@ -38,6 +39,12 @@ _F32 = np.float32
 def _default_decode(path):
     from PIL import Image
     return Image.open(path).convert("RGB")
+
+
+def _default_probe(path):
+    from PIL import Image
+    with Image.open(path) as im:                             # the header only: no pixel is decoded
+        return im.size
 
 
 def _as_crop(img, what):
@@ -166,14 +173,19 @@ def pack_layout(shapes):
     return p
 
 
-def pack_batch(buf, p, crops, hots, points):
-    """Fill a uint8 numpy buffer of at least p.nbytes bytes (the pinned staging): crops [(h, w, 3) uint8] back to back, unaligned."""
+def pack_batch(buf, p, crops, hots, points, pooled=None, base=0):
+    """Fill a uint8 numpy buffer of at least p.nbytes bytes (the pinned staging): crops [(h, w, 3) uint8] back to back, unaligned.
+    With a frame cache, `pooled[b]` is (offset, h, w) for a crop that already lies in the pool (its entry of `crops` is None) and
+    `base` is where the staged crops will lie in the same buffer: every descriptor's offset is then relative to the pool."""
     desc = buf[p.desc_off:p.desc_off + p.B * DESC * 4].view(np.int32).reshape(p.B, DESC)
     desc[:] = 0
     s = 0
     for b, (c, hot) in enumerate(zip(crops, hots)):
-        desc[b, 0:3] = s, c.shape[0], c.shape[1]
         desc[b, 4:4 + 2 * NUM_KPT] = np.asarray(hot, np.int32).reshape(-1)
+        if c is None:
+            desc[b, 0:3] = pooled[b]
+            continue
+        desc[b, 0:3] = base + s, c.shape[0], c.shape[1]
         n = c.shape[0] * c.shape[1] * 3
         buf[p.pix_off + s:p.pix_off + s + n] = c.reshape(-1)
         s += n
@@ -201,15 +213,16 @@ def check_size(target_image_size):
     return size
 
 
-def launch_batch(dev_buf, host_buf, p, size, stream):
+def launch_batch(dev_buf, host_buf, p, size, stream, pool=None):
     """Enqueue csrc/kptload.hip's launch on `stream` for a staged batch already copied to `dev_buf` (device uint8)
-    -> (imgs [B,3,S,S], heatmaps [B,7,S,S])."""
+    -> (imgs [B,3,S,S], heatmaps [B,7,S,S]).  `pool` (device uint8): the descriptors' offsets are relative to it, not to dev_buf's pixels."""
     L = _lib.lib()
     dev = dev_buf.device
     imgs = torch.empty(p.B, 3, size, size, dtype=torch.float32, device=dev)
     hm = torch.empty(p.B, NUM_KPT, size, size, dtype=torch.float32, device=dev)
     base = dev_buf.data_ptr()
-    L.check(L.kptload_batch(host_buf.ctypes.data + p.desc_off, base + p.desc_off, p.B, base + p.pix_off, p.src_bytes, size,
+    src, src_bytes = (base + p.pix_off, p.src_bytes) if pool is None else (pool.data_ptr(), int(pool.numel()))
+    L.check(L.kptload_batch(host_buf.ctypes.data + p.desc_off, base + p.desc_off, p.B, src, src_bytes, size,
                             imgs.data_ptr(), hm.data_ptr(), stream.cuda_stream), "kptload_batch")
     return imgs, hm
 
@@ -249,9 +262,19 @@ class ConeCropBatches:
     the original crop).  `target_image_size`: S or (S, S), 16 <= S <= 256.  `decode(path)` -> a PIL image or an (H, W, 3) uint8 RGB
     array (default: `PIL.Image.open(path).convert('RGB')`), run on `num_workers` threads.  With `prefetch`, batch i+1 is decoded and
     staged while batch i is consumed; its copy and launch run on a side stream that the consumer's stream waits for when the batch is
-    handed over.  `.incorrect_labels` collects the names whose labels give an all-NaN heat-map (module docstring)."""
+    handed over.  `.incorrect_labels` collects the names whose labels give an all-NaN heat-map (module docstring).
 
-    def __init__(self, images, labels, dataset_path, target_image_size, batch_size, decode=None, num_workers=None, device=None, prefetch=True):
+    `cache_bytes`: None, or the HBM budget of a device-resident crop cache (mdcv/data/framecache.py): a crop is decoded
+    once in the loader's lifetime and read from the pool afterwards; same outputs.  The label CSV has no sizes, so the constructor asks
+    `probe(path)` -> (w, h) for each file (default: the image header through Pillow, no pixel decoded) and admits in file order.  The
+    pool is the launch's `src`, whose offsets are `int`s: it ends below 2^31 bytes and crops beyond that are staged.  The budget bounds
+    the cached crops; the allocation is larger by a tail, the bytes of the largest batch as probed, where a batch's staged crops lie
+    under the same `src` (so `cache_bytes=0` allocates the tail and caches nothing).  A cached file that decodes to another size than
+    probed is staged every time; a batch whose staged crops outgrow the tail, because uncached files decode larger than probed, raises
+    ValueError.  `cache_stats()` counts what happened; `close()` frees the pool."""
+
+    def __init__(self, images, labels, dataset_path, target_image_size, batch_size, decode=None, num_workers=None, device=None, prefetch=True,
+                 cache_bytes=None, probe=None):
         if len(images) != len(labels):
             raise ValueError(f"ConeCropBatches: {len(images)} images for {len(labels)} labels")
         self.images = [str(n) for n in images]
@@ -269,19 +292,43 @@ class ConeCropBatches:
         self.incorrect_labels = []
         self._pool = None
         self._slots = [_Slot() for _ in range(3)]
+        self._cache, self._last_ready = None, None
+        if cache_bytes is not None:
+            probe = probe or _default_probe
+            paths = [os.path.join(dataset_path, n) for n in self.images]
+            known = {}
+            for f in paths:
+                if f not in known:
+                    known[f] = tuple(int(v) for v in probe(f))
+            sizes = [known[f] for f in paths]
+            # behind the slots: room for one batch's staged crops, so that one `src` covers both kinds (one launch per batch)
+            per = [sum(3 * w * h for w, h in sizes[i:i + self.batch_size]) for i in range(0, len(sizes), self.batch_size)]
+            tail = framecache._round(max(per, default=0) + 1)
+            self._cache = framecache.FrameCache(paths, sizes, cache_bytes, limit=(1 << 31) - 1 - tail, tail=tail)
+
+    def cache_stats(self):
+        """None without `cache_bytes`; else hits / fills (samples that read the pool without / after decoding their file), misses by
+        reason (samples staged the old way), bytes_reserved (by admission) and pool_bytes (allocated, the staging tail included)."""
+        return None if self._cache is None else self._cache.stats()
 
     def __len__(self):
         return (len(self.images) + self.batch_size - 1) // self.batch_size
 
     # -- host half: decode, labels, stage
     def _sample(self, index):
+        """-> (crop or None, hot pixels, points, NaN-map flag, (h, w), cache entry or None): a cached crop has only its entry"""
         name = self.images[index]
-        crop = _as_crop(self.decode(os.path.join(self.dataset_path, name)), name)
-        h, w = crop.shape[:2]
+        path = os.path.join(self.dataset_path, name)
+        crop = ent = None
+        if self._cache is not None:
+            ent, crop = self._cache.lookup(path, lambda f: _as_crop(self.decode(f), name))
+        else:
+            crop = _as_crop(self.decode(path), name)
+        h, w = crop.shape[:2] if ent is None else (ent.size[1], ent.size[0])
         if h > MAX_SIDE or w > MAX_SIDE:
             raise ValueError(f"{name}: a {h}x{w} crop is over the loader's bound of {MAX_SIDE} px a side")
         hot = hot_pixels(self.labels[index], h, w, name)
-        return crop, hot, scale_points(self.labels[index], h, w, self.size), zero_sum_maps(hot, h, w, self.size).any()
+        return crop, hot, scale_points(self.labels[index], h, w, self.size), zero_sum_maps(hot, h, w, self.size).any(), (h, w), ent
 
     def _stage(self, bi, slot):
         idx = range(bi * self.batch_size, min(len(self.images), (bi + 1) * self.batch_size))
@@ -295,15 +342,30 @@ class ConeCropBatches:
                 print(self.images[i])
                 if self.images[i] not in self.incorrect_labels:
                     self.incorrect_labels.append(self.images[i])
-        crops = [g[0] for g in got]
-        p = pack_layout([c.shape[:2] for c in crops])
+        crops, ents = [g[0] for g in got], [g[5] for g in got]
+        p = pack_layout([(0, 0) if c is None else c.shape[:2] for c in crops])
+        p.fills, need, pooled, base = [], p.nbytes, None, 0
+        if self._cache is not None:
+            c = self._cache
+            base = c.bytes_reserved                              # the tail of the pool: this batch's staged crops
+            if p.src_bytes > c.tail:
+                raise ValueError(f"batch {bi}: {p.src_bytes} bytes of staged crops, the cache planned for {c.tail} (a file decodes larger "
+                                 f"than `probe` said)")
+            pooled = [None if e is None else (e.offset, e.size[1], e.size[0]) for e in ents]
+            for e in c.take_fills(ents):                         # first sight: the whole crops ride behind the batch, one copy each
+                p.fills.append((e, need))
+                need = _align(need + e.nbytes)
         if slot.event is not None:
             slot.event.synchronize()                             # the previous copy out of this buffer has completed
-        if slot.pinned is None or slot.pinned.numel() < p.nbytes:
-            slot.pinned = torch.empty(_align(p.nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        pack_batch(slot.pinned.numpy(), p, crops, [g[1] for g in got], [g[2] for g in got])
+        if slot.pinned is None or slot.pinned.numel() < need:
+            slot.pinned = torch.empty(_align(need, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        host = slot.pinned.numpy()
+        pack_batch(host, p, crops, [g[1] for g in got], [g[2] for g in got], pooled, base)
+        for e, at in p.fills:
+            host[at:at + e.nbytes] = e.frame.reshape(-1)
         names = [self.images[i].split(".")[0] for i in idx]
-        sizes = [torch.tensor([c.shape[a] for c in crops], dtype=torch.int64) for a in range(3)]
+        sizes = [torch.tensor([hw[0] for hw in (g[4] for g in got)], dtype=torch.int64),
+                 torch.tensor([hw[1] for hw in (g[4] for g in got)], dtype=torch.int64), torch.full((len(got),), 3, dtype=torch.int64)]
         return names, sizes, p, slot
 
     # -- device half: one H2D copy and the launch on the side stream
@@ -311,15 +373,28 @@ class ConeCropBatches:
         names, sizes, p, slot = staged
         dev = self.device
         with torch.cuda.device(dev), torch.cuda.stream(self._stream):
-            dbuf = torch.empty(p.nbytes, dtype=torch.uint8, device=dev)
-            dbuf.copy_(slot.pinned[:p.nbytes], non_blocking=True)
+            pool = None
+            if self._cache is None:
+                dbuf = torch.empty(p.nbytes, dtype=torch.uint8, device=dev)
+                dbuf.copy_(slot.pinned[:p.nbytes], non_blocking=True)
+            else:                                                # descriptors and points to the batch's buffer, every pixel to the pool
+                pool, tail = self._cache.pool, self._cache.bytes_reserved
+                dbuf = torch.empty(p.pix_off, dtype=torch.uint8, device=dev)
+                dbuf.copy_(slot.pinned[:p.pix_off], non_blocking=True)
+                if p.src_bytes:
+                    pool[tail:tail + p.src_bytes].copy_(slot.pinned[p.pix_off:p.pix_off + p.src_bytes], non_blocking=True)
+                for e, at in p.fills:
+                    pool[e.offset:e.offset + e.nbytes].copy_(slot.pinned[at:at + e.nbytes], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._stream)
             slot.event = ev
-            imgs, hm = launch_batch(dbuf, slot.pinned.numpy(), p, self.size, self._stream)
+            if self._cache is not None:
+                self._cache.filled([e for e, _ in p.fills], ev)
+            imgs, hm = launch_batch(dbuf, slot.pinned.numpy(), p, self.size, self._stream, pool)
             pts = dbuf[p.pts_off:p.pts_off + p.B * NUM_KPT * 8].view(torch.float32).view(p.B, NUM_KPT, 2).clone()
             ready = torch.cuda.Event()
             ready.record(self._stream)
+            self._last_ready = ready
         return imgs, hm, pts, names, sizes, ready
 
     @property
@@ -332,6 +407,14 @@ class ConeCropBatches:
         _lib.require_gpu()
         dev = self.device
         self._stream = torch.cuda.Stream(dev)
+        if self._cache is not None:
+            self._cache.restart()
+            if self._cache.pool is None:
+                with torch.cuda.device(dev):
+                    self._cache.ensure_pool(dev)                 # allocated on the consumer's stream, written on the side streams
+                    self._stream.wait_stream(torch.cuda.current_stream(dev))
+            if self._last_ready is not None:                     # an earlier epoch's stream: its fills, and its last launch reading the tail
+                self._stream.wait_event(self._last_ready)
         nb = len(self)
         if self.num_workers > 1 and self._pool is None:
             self._pool = ThreadPoolExecutor(self.num_workers, thread_name_prefix="mdcv-decode")
@@ -358,3 +441,8 @@ class ConeCropBatches:
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
+        if self._cache is not None:
+            if self._cache.pool is not None and getattr(self, "_stream", None) is not None:
+                self._cache.pool.record_stream(self._stream)     # the last epoch's launch may still read it
+            self._cache.close()
+            self._last_ready = None

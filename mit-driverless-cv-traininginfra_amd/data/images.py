@@ -43,10 +43,13 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import framecache
 
 PRECISION_BITS = 22                      # Pillow Resample.c: 32 - 8 - 2
 DESC = 20                                # MDCV_IMGLOAD_DESC
 AUG_DESC = 24                            # MDCV_IMGAUG_DESC
+FREF = 4                                 # MDCV_IMGLOAD_FREF
+STAGED = (-1, 0, 0, 0)                   # a frame reference that says: this image's window is in the staging buffer
 LANCZOS, BILINEAR = "lanczos", "bilinear"
 UNSUPPORTED = ("blur", "noise", "contrast", "sharpen", "salt")
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3        # ColorJitter.get_params appends its four ops in this order
@@ -471,9 +474,20 @@ class _Packed:
     pass
 
 
-def pack_layout(geoms, windows_nbytes, num_targets):
+def frame_reference(geom, offset):
+    """The MDCV_IMGLOAD_FREF words of a sample whose whole frame lies at byte `offset` of the pool: (off, pitch, x0, y0).  An empty
+    window reads nothing; its origin (which may lie outside the frame) is replaced by (0, 0)."""
+    x, y, w, h = geom.window
+    if w == 0 or h == 0:
+        x = y = 0
+    return (int(offset), 3 * geom.frame[0], x, y)
+
+
+def pack_layout(geoms, windows_nbytes, num_targets, frefs=None):
     """Byte layout of one batch's staging buffer: [descriptors][labels][coefficient tables][pixels], and behind them, only when a
-    sample of the batch is augmented, [augmentation descriptors] (a batch without one is laid out exactly as before)."""
+    sample of the batch is augmented, [augmentation descriptors] (a batch without one is laid out exactly as before).  `frefs` (one
+    frame reference per sample, `STAGED` for a staged one; a pooled sample's window has 0 bytes): the batch reads a frame cache, and
+    [frame references] come last."""
     p = _Packed()
     B = len(geoms)
     p.B, p.T = B, num_targets
@@ -488,13 +502,17 @@ def pack_layout(geoms, windows_nbytes, num_targets):
     if p.aug:
         p.aug_off = p.nbytes
         p.nbytes = _align(p.aug_off + B * AUG_DESC * 4)
+    p.fref = frefs is not None
+    if p.fref:
+        p.fref_off = p.nbytes
+        p.nbytes = _align(p.fref_off + B * FREF * 8)
     p.max_scr_w = max(g.desc[7] for g in geoms)
     p.max_scr_h = max(g.desc[8] for g in geoms)
     return p
 
 
-def pack_batch(buf, p, geoms, windows, labels=None):
-    """Fill a uint8 numpy buffer of at least p.nbytes bytes (the pinned staging) with the batch."""
+def pack_batch(buf, p, geoms, windows, labels=None, frefs=None):
+    """Fill a uint8 numpy buffer of at least p.nbytes bytes (the pinned staging) with the batch; a pooled sample's window is None."""
     desc = buf[p.desc_off:p.desc_off + p.B * DESC * 4].view(np.int32).reshape(p.B, DESC)
     coefs = buf[p.coef_off:p.coef_off + p.n_coefs * 4].view(np.int32)
     c, s = 0, 0
@@ -508,34 +526,51 @@ def pack_batch(buf, p, geoms, windows, labels=None):
         coefs[c:c + g.row.size] = g.row.reshape(-1)
         c += g.row.size
         desc[b] = d
-        buf[p.pix_off + s:p.pix_off + s + w.nbytes] = w.reshape(-1)
-        s += w.nbytes
+        if w is not None:
+            buf[p.pix_off + s:p.pix_off + s + w.nbytes] = w.reshape(-1)
+            s += w.nbytes
     if p.aug:
         aug = buf[p.aug_off:p.aug_off + p.B * AUG_DESC * 4].view(np.int32).reshape(p.B, AUG_DESC)
         for b, g in enumerate(geoms):
             aug[b] = aug_descriptor(getattr(g, "aug", None))
+    if p.fref:
+        buf[p.fref_off:p.fref_off + p.B * FREF * 8].view(np.int64).reshape(p.B, FREF)[:] = np.asarray(frefs, np.int64).reshape(p.B, FREF)
     if p.T and labels is not None:
         buf[p.lab_off:p.lab_off + p.B * p.T * 20].view(np.float32)[:] = np.asarray(labels, np.float32).reshape(-1)
 
 
-def launch_batch(dev_buf, host_buf, p, channels, height, width, stream):
+def launch_batch(dev_buf, host_buf, p, channels, height, width, stream, pool=None):
     """Enqueue the kernels on `stream` for a staged batch already copied to `dev_buf` (device uint8) -> imgs [B,C,H,W]: the pair of
-    csrc/imgload.hip, or csrc/imgaug.hip's sequence when the batch carries augmentation descriptors."""
+    csrc/imgload.hip, or csrc/imgaug.hip's sequence when the batch carries augmentation descriptors.  A batch with frame references
+    goes through the two `_frames_` entry points with `pool` (device uint8, or None): the same launches."""
     L = _lib.lib()
     dev = dev_buf.device
     imgs = torch.empty(p.B, channels, height, width, dtype=torch.float32, device=dev)
     wsb = L.imgload_workspace_bytes(p.B, p.max_scr_w, p.max_scr_h)
     ws = torch.empty(max(int(wsb), 1), dtype=torch.uint8, device=dev)
     base = dev_buf.data_ptr()
+    hb = host_buf.ctypes.data
+    if p.fref:
+        frames = (hb + p.fref_off, base + p.fref_off)
+        source = (base + p.pix_off, p.src_bytes, pool.data_ptr() if pool is not None else None, int(pool.numel()) if pool is not None else 0)
     if p.aug:
         awb = L.imgaug_workspace_bytes(p.B, height, width)
         if awb < 0:
             raise ValueError(f"augmented batches need 0 < H * W <= 4096 * 4096, got {height}x{width}")
         aws = torch.empty(int(awb), dtype=torch.uint8, device=dev)
-        hb = host_buf.ctypes.data
+        if p.fref:
+            L.check(L.imgload_aug_frames_batch(hb + p.desc_off, base + p.desc_off, *frames, hb + p.aug_off, base + p.aug_off, p.B,
+                                               base + p.coef_off, p.n_coefs, *source, p.max_scr_w, p.max_scr_h, channels, height, width,
+                                               ws.data_ptr(), aws.data_ptr(), imgs.data_ptr(), stream.cuda_stream), "imgload_aug_frames_batch")
+            return imgs
         L.check(L.imgload_aug_batch(hb + p.desc_off, base + p.desc_off, hb + p.aug_off, base + p.aug_off, p.B, base + p.coef_off, p.n_coefs,
                                     base + p.pix_off, p.src_bytes, p.max_scr_w, p.max_scr_h, channels, height, width, ws.data_ptr(),
                                     aws.data_ptr(), imgs.data_ptr(), stream.cuda_stream), "imgload_aug_batch")
+        return imgs
+    if p.fref:
+        L.check(L.imgload_frames_batch(hb + p.desc_off, base + p.desc_off, *frames, p.B, base + p.coef_off, p.n_coefs, *source, p.max_scr_w,
+                                       p.max_scr_h, channels, height, width, ws.data_ptr(), imgs.data_ptr(), stream.cuda_stream),
+                "imgload_frames_batch")
         return imgs
     L.check(L.imgload_batch(host_buf.ctypes.data + p.desc_off, base + p.desc_off, p.B, base + p.coef_off, p.n_coefs, base + p.pix_off,
                             p.src_bytes, p.max_scr_w, p.max_scr_h, channels, height, width, ws.data_ptr(), imgs.data_ptr(),
@@ -543,18 +578,25 @@ def launch_batch(dev_buf, host_buf, p, channels, height, width, stream):
     return imgs
 
 
-def transform_batch(frames, geoms, bw=False, device=None):
+def transform_batch(frames, geoms, bw=False, device=None, pool=None, offsets=None):
     """Synchronous convenience (tests, probes): decoded frames [(H, W, 3) uint8] + their geometries (each may carry `.aug`, an
-    `Augmentation` with its matrix set) -> imgs [B,C,H,W] fp32 on the device."""
+    `Augmentation` with its matrix set) -> imgs [B,C,H,W] fp32 on the device.  With `pool` (device uint8) and `offsets` (per sample: the
+    byte offset in `pool` at which its whole frame already lies, rows of 3 * frame width bytes; None: stage the window from `frames`),
+    pooled samples are read in place and their entry of `frames` is not looked at."""
     _lib.require_gpu()
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    windows = [crop_window(f, g) for f, g in zip(frames, geoms)]
-    p = pack_layout(geoms, [w.nbytes for w in windows], 0)
+    if pool is None:
+        frefs = None
+        windows = [crop_window(f, g) for f, g in zip(frames, geoms)]
+    else:
+        frefs = [STAGED if o is None else frame_reference(g, o) for g, o in zip(geoms, offsets)]
+        windows = [crop_window(f, g) if o is None else None for f, g, o in zip(frames, geoms, offsets)]
+    p = pack_layout(geoms, [0 if w is None else w.nbytes for w in windows], 0, frefs)
     host = np.zeros(p.nbytes, np.uint8)
-    pack_batch(host, p, geoms, windows)
+    pack_batch(host, p, geoms, windows, frefs=frefs)
     with torch.cuda.device(device):
         dev = torch.from_numpy(host).to(device)
-        return launch_batch(dev, host, p, 1 if bw else 3, geoms[0].height, geoms[0].width, torch.cuda.current_stream(device))
+        return launch_batch(dev, host, p, 1 if bw else 3, geoms[0].height, geoms[0].width, torch.cuda.current_stream(device), pool)
 
 
 def _default_decode(path):
@@ -579,11 +621,16 @@ class ImageLabelBatches:
     loaders, so the training loader's subset is the one train.py draws.  `debug_mode` forces patch 0 as the reference does (the patch
     draw still happens first, so the flip draw is unchanged).  With `prefetch`, batch i+1 is decoded and
     staged while batch i is consumed; its copy runs on a side stream that the consumer's stream waits for when the batch is handed over.
+
+    `cache_bytes`: None, or the HBM budget of a device-resident frame cache (mdcv/data/framecache.py).  Files are admitted
+    in CSV order by their CSV sizes until the budget is used; an admitted file is decoded once in the loader's lifetime, its whole frame
+    stays on the device, and from then on its samples stage no pixels: the resize reads their windows in place.  The batches are the
+    same bytes with and without it.  `cache_stats()` counts what happened; `close()` frees the pool.
     """
 
     def __init__(self, path, dataset_path, width, height, num_images=-1, bw=False, lr_flip=False, ts=True, batch_size=1, shuffle=True,
                  num_workers=None, seed=0, device=None, decode=None, ud_flip=False, subset_seed=0, draws=None, prefetch=True, debug_mode=False,
-                 augment_hsv=False, augment_affine=False, data_aug=False, **options):
+                 augment_hsv=False, augment_affine=False, data_aug=False, cache_bytes=None, **options):
         bad = [k for k in UNSUPPORTED if options.pop(k, False)]
         if bad:
             raise ValueError(f"ImageLabelBatches does not implement {', '.join(bad)} (imgaug augmentations); set them False")
@@ -617,6 +664,12 @@ class ImageLabelBatches:
         self.epoch = 0
         self._pool = None
         self._slots = [_Slot() for _ in range(3)]
+        self._cache = None if cache_bytes is None else framecache.FrameCache(self.img_files, self.sizes, cache_bytes)
+
+    def cache_stats(self):
+        """None without `cache_bytes`; else hits / fills (samples that read the pool without / after decoding their file), misses by
+        reason (samples staged the old way), bytes_reserved (by admission) and pool_bytes (allocated)."""
+        return None if self._cache is None else self._cache.stats()
 
     def __len__(self):
         return (len(self.img_files) + self.batch_size - 1) // self.batch_size
@@ -660,13 +713,23 @@ class ImageLabelBatches:
         return g
 
     # -- host half: decode, plan, crop, stage
-    def _sample(self, epoch, index):
-        img = self.decode(self.img_files[index])
+    def _decode(self, path):
+        img = self.decode(path)
         frame = img if isinstance(img, np.ndarray) else np.asarray(img, dtype=np.uint8)
         if frame.ndim != 3 or frame.shape[2] < 3 or frame.dtype != np.uint8:
-            raise ValueError(f"{self.img_files[index]}: decode must give an (H, W, 3) uint8 RGB frame, got {frame.shape} {frame.dtype}")
+            raise ValueError(f"{path}: decode must give an (H, W, 3) uint8 RGB frame, got {frame.shape} {frame.dtype}")
+        return frame
+
+    def _sample(self, epoch, index):
+        """-> (geometry, window bytes or None, cache entry or None): a sample of a cached frame has no window, only its entry"""
+        if self._cache is not None:
+            ent, frame = self._cache.lookup(self.img_files[index], self._decode)
+            if ent is not None:
+                return self.plan(index, epoch, ent.size), None, ent
+        else:
+            frame = self._decode(self.img_files[index])
         g = self.plan(index, epoch, (frame.shape[1], frame.shape[0]))
-        return g, crop_window(frame, g)
+        return g, crop_window(frame, g), None
 
     def _stage(self, epoch, bi, slot):
         order = self._orders[epoch]
@@ -675,14 +738,24 @@ class ImageLabelBatches:
             got = list(self._pool.map(lambda i: self._sample(epoch, i), idx))
         else:
             got = [self._sample(epoch, i) for i in idx]
-        geoms, windows = [g for g, _ in got], [w for _, w in got]
-        p = pack_layout(geoms, [w.nbytes for w in windows], self.num_targets_per_image)
+        geoms, windows, ents = [g for g, _, _ in got], [w for _, w, _ in got], [e for _, _, e in got]
+        frefs, fills = None, []
+        if any(e is not None for e in ents):                     # a batch with no cached sample is staged and launched as without a cache
+            frefs = [STAGED if e is None else frame_reference(g, e.offset) for g, e in zip(geoms, ents)]
+            fills = self._cache.take_fills(ents)
+        p = pack_layout(geoms, [0 if w is None else w.nbytes for w in windows], self.num_targets_per_image, frefs)
+        p.fills, need = [], p.nbytes                             # first sight: the whole frames ride behind the batch, one copy each
+        for e in fills:
+            p.fills.append((e, need))
+            need = _align(need + e.nbytes)
         if slot.event is not None:
             slot.event.synchronize()                             # the previous copy out of this buffer has completed
-        if slot.pinned is None or slot.pinned.numel() < p.nbytes:
-            slot.pinned = torch.empty(_align(p.nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        if slot.pinned is None or slot.pinned.numel() < need:
+            slot.pinned = torch.empty(_align(need, 1 << 20), dtype=torch.uint8, pin_memory=True)
         host = slot.pinned.numpy()
-        pack_batch(host, p, geoms, windows, [g.labels for g in geoms])
+        pack_batch(host, p, geoms, windows, [g.labels for g in geoms], frefs)
+        for e, at in p.fills:
+            host[at:at + e.nbytes] = e.frame.reshape(-1)
         return [g.uri for g in geoms], p, slot
 
     # -- device half: one H2D copy and the kernel pair on the side stream
@@ -692,10 +765,17 @@ class ImageLabelBatches:
         with torch.cuda.device(dev), torch.cuda.stream(self._stream):
             dbuf = torch.empty(p.nbytes, dtype=torch.uint8, device=dev)
             dbuf.copy_(slot.pinned[:p.nbytes], non_blocking=True)
+            pool = None
+            if p.fref:
+                pool = self._cache.pool
+                for e, at in p.fills:                            # pinned -> the file's slot, in front of this batch's kernels
+                    pool[e.offset:e.offset + e.nbytes].copy_(slot.pinned[at:at + e.nbytes], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._stream)
             slot.event = ev
-            imgs = launch_batch(dbuf, slot.pinned.numpy(), p, self.channels, self.height, self.width, self._stream)
+            if p.fref:
+                self._cache.filled([e for e, _ in p.fills], ev)
+            imgs = launch_batch(dbuf, slot.pinned.numpy(), p, self.channels, self.height, self.width, self._stream, pool)
             tg = dbuf[p.lab_off:p.lab_off + p.B * p.T * 20].view(torch.float32).view(p.B, p.T, 5).clone()
             ready = torch.cuda.Event()
             ready.record(self._stream)
@@ -714,6 +794,14 @@ class ImageLabelBatches:
         self._orders = {epoch: self.order(epoch)}
         dev = self.device
         self._stream = torch.cuda.Stream(dev)
+        if self._cache is not None:
+            self._cache.restart()
+            if self._cache.pool is None:
+                with torch.cuda.device(dev):
+                    if self._cache.ensure_pool(dev) is not None:  # allocated on the consumer's stream, written on the side streams
+                        self._stream.wait_stream(torch.cuda.current_stream(dev))
+            if self._cache.last_fill is not None:                # slots filled on an earlier epoch's stream, read on this one
+                self._stream.wait_event(self._cache.last_fill)
         nb = len(self)
         if self.num_workers > 1 and self._pool is None:
             self._pool = ThreadPoolExecutor(self.num_workers, thread_name_prefix="mdcv-decode")
@@ -740,3 +828,7 @@ class ImageLabelBatches:
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
+        if self._cache is not None:
+            if self._cache.pool is not None and getattr(self, "_stream", None) is not None:
+                self._cache.pool.record_stream(self._stream)     # the last epoch's kernels may still read it
+            self._cache.close()

@@ -4,6 +4,8 @@
     device events (several timings of 200 launches each), beside its byte floor; one more launch under the in-library profiler
 (b) the whole loader with the default decoder (PNG crops written to a temporary directory), img/s on 1 / 8 / 16 decode threads
 (c) ms per KeypointNet + CrossRatioLoss + FusedAdam bf16 B=256 train step fed by the loader against the same step fed by SyntheticConeCrops
+(d) the crop cache (`cache_bytes`): the whole loader of (b) without it, in its fill epoch and in hit epochs, and the step of (c)
+    fed from hit epochs
 
 usage: kpt_loader_probe.py [files (default 1024)] [parts, default abc]"""
 import ctypes
@@ -153,18 +155,73 @@ def part_c(tmp, names, labels, steps=10):
               f"{real:6.2f} ms/step ({1e3 * B / real:7.0f} img/s)")
 
 
+def part_d(tmp, names, labels, steps=10):
+    print(f"(d) crop cache, PNG crops, B={B} S={S}, 16 threads (whole-loader img/s per epoch)")
+
+    def epoch(ld):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n = sum(b[0].shape[0] for b in ld)
+        torch.cuda.synchronize()
+        return n / (time.perf_counter() - t0)
+    ld = C.ConeCropBatches(names, labels, tmp, S, B, num_workers=16)
+    plain = [epoch(ld) for _ in range(3)]
+    ld.close()
+    t0 = time.perf_counter()
+    ld = C.ConeCropBatches(names, labels, tmp, S, B, num_workers=16, cache_bytes=1 << 30)
+    built = time.perf_counter() - t0
+    cached = [epoch(ld) for _ in range(4)]
+    print("    no cache: " + " / ".join(f"{r:.0f}" for r in plain) + " img/s   cache: fill epoch " + f"{cached[0]:.0f}, hit epochs "
+          + " / ".join(f"{r:.0f}" for r in cached[1:]) + f" img/s   (constructor with the header probe of {len(names)} files: {built:.2f} s)")
+    print(f"    {ld.cache_stats()}")
+    from mdcv.optim import FusedAdam
+    from mdcv.rektnet.cross_ratio_loss import CrossRatioLoss
+    from mdcv.rektnet.keypoint_net import KeypointNet
+    torch.manual_seed(0)
+    kp = KeypointNet(7, (S, S), precision="bf16").cuda().train()
+    crit = CrossRatioLoss("l1_softargmax", True, 0.05, 0.05)
+    opt = FusedAdam(kp, lr=1e-3)
+
+    def run(data):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        i = 0
+        while i < 3 + steps:
+            for x, hm_t, pts_t, _, _ in data:
+                if x.shape[0] != B:
+                    continue
+                if i == 3:
+                    s.record()
+                opt.zero_grad()
+                hm, pts = kp(x)
+                crit(hm, pts, hm_t, pts_t)[2].backward()
+                opt.step()
+                i += 1
+                if i == 3 + steps:
+                    break
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e) / steps
+    syn = run(SyntheticConeCrops(B, S, batches=steps + 4, seed=3))
+    hit = run(ld)
+    ld.close()
+    print(f"    KeypointNet bf16 step: SyntheticConeCrops {syn:6.2f} ms/step ({1e3 * B / syn:7.0f} img/s)   cached ConeCropBatches, hit epochs: "
+          f"{hit:6.2f} ms/step ({1e3 * B / hit:7.0f} img/s)")
+
+
 def main():
     torch.cuda.set_device(0)
     samples = [crop(i) for i in range(max(NFILES, B))]
     if "a" in PARTS:
         part_a(samples)
-    if "b" in PARTS or "c" in PARTS:
+    if "b" in PARTS or "c" in PARTS or "d" in PARTS:
         with tempfile.TemporaryDirectory() as tmp:
             names, labels = write_dataset(tmp, samples[:NFILES])
             if "b" in PARTS:
                 part_b(tmp, names, labels)
             if "c" in PARTS:
                 part_c(tmp, names, labels)
+            if "d" in PARTS:
+                part_d(tmp, names, labels)
 
 
 if __name__ == "__main__":

@@ -7,6 +7,9 @@
 (d) the augmented transform (csrc/imgaug.hip) alone, B=32 of 416x416 from 1920x1080 frames, tile-and-scale at scale 1.0: no augmentation
     (the two-launch path), affine only, jitter + affine as data_aug draws them; each row several times over to show the run-to-run spread
 
+(e) the frame cache (`cache_bytes`): the step of (c) fed without the cache, in the cache's fill epoch and in hit epochs, beside
+    SyntheticCones on the same lease; staged bytes per batch with and without; the hit-epoch loader alone (img/s, host ms per batch)
+
 Device events after a warm-up, profiler off.  usage: loader_probe.py [files per format (default 32)] [parts, default abcd]"""
 import contextlib
 import ctypes
@@ -170,6 +173,86 @@ def part_c(tmp, csv_path, steps=10):
     print(f"    SyntheticCones: {syn:7.2f} ms/step   ImageLabelBatches (JPEG, 16 threads, data_aug): {real:7.2f} ms/step")
 
 
+def part_e(tmp, csv_path, steps=10):
+    print(f"(e) frame cache: YOLOv3 416x416 B=32 bf16 train step, JPEG, 16 threads, shuffle (ms/step over {steps} steps after 3 warm-up "
+          f"steps; the fill epoch from its first batch)")
+    from mdcv.optim import FusedAdam
+    from mdcv.yolo.models import Darknet
+    d = tempfile.mkdtemp()
+    cfg = bench.write_yolo_cfg(d, classes=1)
+    cwd = os.getcwd()
+    os.chdir(d)
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        net = Darknet(cfg, 2.0, 1.6, 25.0, 0.1, True, precision="bf16").cuda().train()
+    os.chdir(cwd)
+    opt = FusedAdam(net, lr=1e-4)
+
+    def run(data, warm=3):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if warm == 0:
+            s.record()
+        for i, (_, x, tg) in enumerate(data):
+            if i == warm and warm:
+                s.record()
+            opt.zero_grad()
+            out = net(x, tg)
+            out[0].sum().backward()
+            opt.step()
+            if i == warm + steps - 1:
+                e.record()
+                break
+        e.synchronize()
+        return s.elapsed_time(e) / steps
+
+    staged = []
+    layout = I.pack_layout
+
+    def recording_layout(*a, **k):
+        p = layout(*a, **k)
+        staged.append(p.nbytes)
+        return p
+    I.pack_layout = recording_layout
+    try:
+        syn = run(SyntheticCones(B, S, S, 16, 1, batches=steps + 4, seed=3))
+        ld = I.ImageLabelBatches(csv_path, tmp, S, S, ts=True, lr_flip=False, batch_size=B, num_workers=16)
+        assert len(ld) >= steps + 3, "more files: an epoch must hold the timed steps"
+        plain = run(ld)
+        ld.close()
+        plain_mib = np.mean(staged) / 2**20
+        ld = I.ImageLabelBatches(csv_path, tmp, S, S, ts=True, lr_flip=False, batch_size=B, num_workers=16, cache_bytes=64 << 30)
+        fill = run(ld, warm=0)
+        fill_stats = ld.cache_stats()
+        del staged[:]
+        hits = [run(ld) for _ in range(3)]
+        hit_mib = np.mean(staged) / 2**20
+        syn2 = run(SyntheticCones(B, S, S, 16, 1, batches=steps + 4, seed=4))
+        print(f"    SyntheticCones {syn:7.2f} ms/step (again at the end: {syn2:7.2f})   no cache {plain:7.2f} ms/step   "
+              f"fill epoch {fill:7.2f} ms/step   hit epochs " + " / ".join(f"{h:.2f}" for h in hits) + " ms/step")
+        print(f"    staged per batch: {plain_mib:7.3f} MiB without the cache, {hit_mib:7.3f} MiB in a hit epoch; after the fill epoch's "
+              f"{steps} steps: {fill_stats}")
+        times = []
+        stage = ld._stage
+
+        def timed_stage(*a):
+            t0 = time.perf_counter()
+            r = stage(*a)
+            times.append(time.perf_counter() - t0)
+            return r
+        ld._stage = timed_stage
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n = sum(x.shape[0] for _, x, _ in ld)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"    hit-epoch loader alone ({len(ld)} batches, 16 threads): {n / dt:7.0f} img/s; host staging (plan, labels, packing) "
+              f"{1e3 * np.mean(times):6.2f} ms/batch")
+        print(f"    {ld.cache_stats()}")
+        ld.close()
+    finally:
+        I.pack_layout = layout
+
+
 def part_d(frames, repeats=5):
     print("(d) augmented transform alone, B=32 outputs of 416x416 RGB from 1920x1080 frames, tile-and-scale at scale 1.0 "
           f"(ms per batch, kernels only; {repeats} timings of 50 batches each)")
@@ -217,13 +300,15 @@ def main():
         part_a(frames)
     if "d" in PARTS:
         part_d(frames)
-    if "b" in PARTS or "c" in PARTS:
+    if "b" in PARTS or "c" in PARTS or "e" in PARTS:
         with tempfile.TemporaryDirectory() as tmp:
             csvs = {fmt: write_dataset(tmp, frames, fmt) for fmt in (("png", "jpg") if "b" in PARTS else ("jpg",))}
             if "b" in PARTS:
                 part_b(tmp, csvs)
             if "c" in PARTS:
                 part_c(tmp, csvs["jpg"])
+            if "e" in PARTS:
+                part_e(tmp, csvs["jpg"])
 
 
 if __name__ == "__main__":
