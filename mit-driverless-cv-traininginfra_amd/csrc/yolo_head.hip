@@ -59,7 +59,14 @@ __global__ void yolo_assign_kernel(const float* __restrict__ tg, const float* __
 
 static unsigned grid_for(long long n) { long long g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+// 1 / (1 + expf(-x)) wherever expf(-x) is finite.  From x = -88.8 down expf(-x) is inf and the quotient 0, while the true value
+// e^x / (1 + e^x) = e^x (1 + e^x rounds to 1) is still a (denormal) fp32 number: with 0, BCE(p, 1) clamps at 100 instead of -x and its
+// gradient vanishes.  Every logit above -88.8 keeps the bits it always had, so a training run without such logits is unchanged.
+// Used by the loss, gradient and decode kernels only: the assignment path has no sigmoid.
+__device__ __forceinline__ float sigmoidf_(float x) {
+  const float e = expf(-x);
+  return e == INFINITY ? expf(x) : 1.f / (1.f + e);
+}
 
 // out[0] += head loss ; out[1..6] += (x,y,w,h,obj,noobj) parts (models.py:199-211,332,338).  A launch of its own: folding it into the
 // last block of the loss kernel needs an agent-scope fence per block, and on eight L2s that tripled the loss kernel (11 -> 33 us).
