@@ -219,6 +219,25 @@ int mdcv_cross_ratio_loss(const float* hm, const float* pts, const float* thm, c
                           int include_geo, float gamma_horz, float gamma_vert, double* acc_ws, const float* gscale, float* out3,
                           float* dpts, float* dhm, void* stream);
 
+/* ---- RektNet validation of a whole batch in ONE launch (csrc/kpt_eval.hip): replaces the per-image loop of eval_model
+ *      (RektNet/train_eval.py:115-138, a DataLoader of batch_size 1 and three .item() per image) and of print_kpt_L2_distance (:140-186).
+ * rows [B][MDCV_KPT_EVAL_ROW] fp32, 16-byte aligned; row i = loc, geo, total, d0 .. d6, 0, 0:
+ *   loc, geo, total   what CrossRatioLoss(loss_type, include_geo, gamma_horz, gamma_vert) returns for sample i ALONE (hm[i:i+1], pts[i:i+1], ...):
+ *                     loc = sum of the 14 squared (0) / absolute (2) point differences, or of the 7 H W squared heat-map differences (1);
+ *                     geo = gamma_horz (hA + hB) / 2 + gamma_vert (vA + vB + vC + vD) / 4, each term 1 - u.v of THIS sample's unit vectors
+ *                     (F.normalize's eps 1e-12: coincident points give a zero vector); geo = 0 and total = loc without include_geo.
+ *                     NOT what mdcv_cross_ratio_loss gives for the batch: its geo is the mean of a [B,B] all-pairs matrix.
+ *   d_k               sqrt((dist_sx (p_kx - t_kx))^2 + (dist_sy (p_ky - t_ky))^2): utils.calculate_distance's pixel distance when the caller
+ *                     passes dist_sx = C input_size[0], dist_sy = C input_size[1] with C = x_batch.shape[1] = 3 -- the reference multiplies
+ *                     the normalised points by the image's CHANNEL count before input_size (train_eval.py:152-157); reproduced, not corrected.
+ * fp32 differences and products, fp64 accumulation, one rounding per output; NaN / Inf stay inside their own sample.  Row i is the same bits
+ * whatever B is and wherever sample i stands in the batch.  loss_type 0 / 2 never read hm / thm (both may be NULL).  Nothing is written
+ * beyond row B - 1.  MDCV_EARG before any launch: NULL pts / tpts / rows, rows not 16-byte aligned, B < 1 or B > 65535, loss_type outside
+ * 0..2, and for loss_type 1 NULL hm / thm, H < 1, W < 1 or 7 H W > INT_MAX. */
+#define MDCV_KPT_EVAL_ROW 12
+int mdcv_kpt_eval_rows(const float* hm, const float* pts, const float* thm, const float* tpts, int B, int H, int W, int loss_type, int include_geo,
+                       float gamma_horz, float gamma_vert, float dist_sx, float dist_sy, float* rows, void* stream);
+
 /* ---- detection post-processing: replaces the per-image Python loop validate.py:80-141, the sequential
  *      greedy NMS utils/nms.py:4-61 and average_precision/compute_ap utils/utils.py:58-119.
  *      Visiting order: descending score, equal scores by descending index (the reference's ascending sort walked from the

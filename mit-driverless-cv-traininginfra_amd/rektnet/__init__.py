@@ -1,1 +1,3 @@
-"""Drop-in for the reference's RektNet hot-path modules (keypoint_net.py, resnet.py, cross_ratio_loss.py)."""
+"""Drop-in for the reference's RektNet hot-path modules (keypoint_net.py, resnet.py, cross_ratio_loss.py), and the batched form of
+train_eval.py's two validation routines (evaluate.py)."""
+from .evaluate import KeypointEvaluator, eval_model, print_kpt_L2_distance  # noqa: F401
