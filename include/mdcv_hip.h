@@ -366,6 +366,31 @@ int mdcv_imgload_aug_frames_batch(const int* desc_host, const int* desc, const l
 int mdcv_kptload_batch(const int* desc_host, const int* desc, int B, const unsigned char* src, long long src_bytes, int S, float* images,
                        float* heatmaps, void* stream);
 
+/* ---- detections drawn into the frames on the device (csrc/detect_draw.hip; the tail of single_img_detect, CVC-YOLOv3/detect.py:99-104:
+ *      four .item() reads and one ImageDraw.rectangle(outline="red") per box on the host).  ONE launch per batch, grid (K, B); slot k of frame b
+ *      does nothing unless k < count[b] (a device int, as mdcv_detect_post writes it), so the host never reads the counts.  Per kept box:
+ *       frame_boxes [B,K,4] double   (double)boxes[b,k,j] / ratio - pad (pad_w for x, pad_h for y) in IEEE double: Python's `x.item() / ratio - pad_w`
+ *       rects       [B,K,4] int32    (int) of those doubles (toward zero: -0.9 -> 0, -1.5 -> -1), or (0, 0, -1, -1) for a box that is NOT
+ *                                    drawn: x1 < x0 or y1 < y0 compared as doubles (where Pillow raises), or any coordinate NaN, +-inf or of
+ *                                    magnitude >= 2^30 (where C's conversion is undefined); skipped[b] counts them (a departure: the
+ *                                    reference's behaviour there is an exception or undefined)
+ *       pool                         the outline, as Pillow 12.2's ImagingDrawRectangle draws it for width 1 without fill: rows y0 and y1 from x0
+ *                                    to x1 inclusive, columns x0 and x1 over every row between y0 + 1 and y1 inclusive in either order (so with
+ *                                    y1 == y0 row y0 + 1 gets the two end pixels), clipped to the frame; bytes (red, green, blue), the same for
+ *                                    every box of the call -- overlapping boxes store identical bytes and no order between them matters
+ *      boxes [B,K,4] fp32 corner boxes in detector coordinates (mdcv_detect_post's out_boxes with K = top_k).  Frames are uint8 HWC RGB with rows
+ *      of 3 * W bytes in `pool`, the layout mdcv_imgload_frames_batch reads.  One descriptor of MDCV_DETECT_DESC long longs per frame:
+ *       [0] off   byte offset of the frame in `pool`   [1] W   [2] H   [3] the bits of the double `ratio`   [4] pad_w   [5] pad_h
+ *      (ratio and the pads: calculate_padding's, mdcv/data/images.py letterbox()).  A descriptor is good when off >= 0, 1 <= W, H <= 2^24,
+ *      off + 3 W H <= pool_bytes, |pad| <= 2^24 and 0 < ratio < 2^30.  desc_host is validated (MDCV_EARG, nothing is enqueued); desc is its
+ *      device copy, whose frame extents the kernel checks again (a frame that fails is not drawn on).  skipped [B] is zeroed by the call (a
+ *      memset on `stream` in front of the launch).  Slots k >= count[b] of frame_boxes / rects are not written.  B == 0 or K == 0: MDCV_OK,
+ *      nothing is enqueued or written.  B, K <= 65535.  No state is kept between calls. */
+#define MDCV_DETECT_DESC 6
+int mdcv_detect_draw_boxes(const long long* desc_host, const long long* desc, int B, const float* boxes, const int* count, int K,
+                           unsigned char* pool, long long pool_bytes, int red, int green, int blue, double* frame_boxes, int* rects,
+                           int* skipped, void* stream);
+
 /* ---- optimizer step over the flat fp32 parameter buffer (train.py:180-187,72 ; train_eval.py:263,72) */
 int mdcv_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr, float beta1,
                    float beta2, float eps, float weight_decay, float grad_scale, void* stream);

@@ -1,0 +1,292 @@
+"""Batched image and frame detection with the boxes drawn on the device: the native counterpart of CVC-YOLOv3/detect.py.
+
+The reference's `single_img_detect` (detect.py:60-111) costs, per frame, a Pillow pad and resize on the host, a batch-1 forward, four
+`.item()` reads per kept box (:100-103) and a host `ImageDraw.rectangle` (:104).  `FrameDetector.detect_frames` runs the same steps over
+batches of decoded frames that stay on the device from the upload to the annotated pixels:
+
+  1. the whole frames of a batch are packed into one pinned buffer at 16-byte-aligned offsets, behind the resize descriptors and tables,
+  2. one H2D copy; the frames' bytes on the device are the batch's frame pool,
+  3. pad-and-resize reads each frame in place from that pool (`sample_geometry(ts=False)`, `mdcv_imgload_frames_batch`: the loaders'
+     byte-exact Pillow resize, nothing new),
+  4. `model.eval()`, forward under `no_grad`,
+  5. `detect_postprocess(output, None, ...)`: confidence filter and NMS of the whole batch, no host round trip,
+  6. `mdcv_detect_draw_boxes` (csrc/detect_draw.hip) on the same stream into the same pool bytes: each kept box mapped to frame
+     coordinates in IEEE double as detect.py:100-103 maps it, truncated as Pillow truncates it, and outlined as Pillow 12.2 outlines it,
+  7. one D2H copy of the pool and the small tables behind it,
+
+with ONE host synchronisation per batch and none per box.  Two staging slots: batch n + 1 is taken from the iterable and packed (on a
+worker thread) while the device works on batch n.
+
+`single_img_detect` and `detect` take the reference's argument lists, so a caller swaps the import.  Departures, all
+documented in DESIGN.md §19: a box Pillow would refuse (x1 < x0, y1 < y0) or C could not convert (NaN, inf, magnitude >= 2^30) is skipped
+and counted instead of raising; a file whose Pillow mode is not RGB raises ValueError (the reference draws on the unconverted image and
+its ink then depends on the mode); with no detection the unannotated image is saved (the reference hits an unbound variable); video
+containers need cv2 and raise ValueError; `detect` also accepts a directory of images, the batched stand-in for the frame-dump video loop.
+"""
+import os
+from concurrent.futures import ThreadPoolExecutor
+from itertools import islice
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..data import images as I
+from .postprocess import detect_postprocess, L_MAX_TOPK
+
+DETECT_DESC = 6                          # MDCV_DETECT_DESC
+IMG_FORMATS = (".jpg", ".jpeg", ".png", ".tif")         # detect.py:122-123
+VID_FORMATS = (".mov", ".avi", ".mp4")
+_align = I._align
+
+
+# ------------------------------------------------------------------------------------------------------------- host layout (no GPU)
+def frame_offsets(sizes):
+    """[(W, H)] -> ([byte offset of each whole frame in the pool, 16-byte aligned], pool bytes)"""
+    offsets, at = [], 0
+    for w, h in sizes:
+        offsets.append(at)
+        at = _align(at + 3 * int(w) * int(h))
+    return offsets, at
+
+
+def detect_descriptors(geoms, offsets):
+    """MDCV_DETECT_DESC long longs per frame (include/mdcv_hip.h): off, W, H, the bits of the double `ratio`, pad_w, pad_h -- ratio and
+    pads are `letterbox()`'s, as the pad-and-resize geometry carries them"""
+    d = np.zeros((len(geoms), DETECT_DESC), np.int64)
+    for b, (g, off) in enumerate(zip(geoms, offsets)):
+        d[b, 0], d[b, 1], d[b, 2] = off, g.frame[0], g.frame[1]
+        d[b, 3] = np.array([g.ratio], np.float64).view(np.int64)[0]
+        d[b, 4], d[b, 5] = g.pad_w, g.pad_h
+    return d
+
+
+class BatchPlan:
+    """Byte layout of one batch.  Device buffer: [resize descriptors, tables and frame references (images.pack_layout)] [detect
+    descriptors] [pool: the whole frames] [frame_boxes B,K,4 f64] [rects B,K,4 i32] [prob B,K f32] [count B i32] [skipped B i32];
+    the pinned input is everything up to the end of the pool, the copy back is everything from the pool (or from the tables) on."""
+
+    def __init__(self, sizes, width, height, K):
+        B = len(sizes)
+        self.B, self.K, self.sizes = B, int(K), [(int(w), int(h)) for w, h in sizes]
+        self.geoms = [I.sample_geometry(w, h, width, height, ts=False) for w, h in self.sizes]
+        self.offsets, self.pool_bytes = frame_offsets(self.sizes)
+        self.frefs = [I.frame_reference(g, o) for g, o in zip(self.geoms, self.offsets)]
+        self.layout = I.pack_layout(self.geoms, [0] * B, 0, self.frefs)
+        self.desc = detect_descriptors(self.geoms, self.offsets)
+        self.det_off = self.layout.nbytes
+        self.pool_off = _align(self.det_off + B * DETECT_DESC * 8)
+        self.in_bytes = self.pool_off + self.pool_bytes
+        self.fb_off = self.in_bytes                                          # 16-byte aligned: pool_off and pool_bytes both are
+        self.rect_off = self.fb_off + B * self.K * 32
+        self.prob_off = self.rect_off + B * self.K * 16
+        self.count_off = _align(self.prob_off + B * self.K * 4)
+        self.skip_off = _align(self.count_off + B * 4)
+        self.nbytes = _align(self.skip_off + B * 4)
+
+    def pack(self, host, frames):
+        """fill the pinned input (uint8 numpy, >= in_bytes) with the batch"""
+        I.pack_batch(host, self.layout, self.geoms, [None] * self.B, frefs=self.frefs)
+        host[self.det_off:self.det_off + self.desc.nbytes].view(np.int64)[:] = self.desc.reshape(-1)
+        for f, off, (w, h) in zip(frames, self.offsets, self.sizes):
+            host[self.pool_off + off:self.pool_off + off + 3 * w * h] = f.reshape(-1)
+
+
+def _check_frame(f, i):
+    f = np.asarray(f)
+    if f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8 or f.shape[0] < 1 or f.shape[1] < 1:
+        raise ValueError(f"detect_frames: frame {i} must be an (H, W, 3) uint8 RGB array, got {f.shape} {f.dtype}")
+    return np.ascontiguousarray(f)
+
+
+class FrameDetections:
+    """One frame's result.  boxes float64 [n,4] (x0, y0, x1, y1 in frame coordinates, most confident first), prob float32 [n], rects int32
+    [n,4] (the truncated boxes as drawn; (0, 0, -1, -1) for a skipped one), skipped (boxes not drawn), annotated (H, W, 3) uint8 -- a
+    NumPy array, or a device tensor with `keep_on_device`."""
+
+    __slots__ = ("boxes", "prob", "rects", "skipped", "annotated")
+
+    def __init__(self, boxes, prob, rects, skipped, annotated):
+        self.boxes, self.prob, self.rects, self.skipped, self.annotated = boxes, prob, rects, skipped, annotated
+
+
+class _Slot:
+    def __init__(self):
+        self.pin_in, self.pin_out = None, None
+
+
+def _pinned(t, need):
+    if t is None or t.numel() < need:
+        t = torch.empty(_align(max(need, 1), 1 << 20), dtype=torch.uint8, pin_memory=True)
+    return t
+
+
+class FrameDetector:
+    """`FrameDetector(model).detect_frames(frames)`: see the module docstring.  conf_thres / nms_thres default to `model.get_threshs()`;
+    at most `max_boxes` (<= top_k) boxes per frame are mapped and drawn, the most confident ones; `outline` is the one RGB triple of a
+    call (default `ImageColor.getrgb("red")`)."""
+
+    def __init__(self, model, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16):
+        conf, nms, _ = model.get_threshs()
+        self.model = model
+        self.conf_thres = float(conf if conf_thres is None else conf_thres)
+        self.nms_thres = float(nms if nms_thres is None else nms_thres)
+        self.top_k, self.max_boxes, self.batch_size = int(top_k), int(max_boxes), int(batch_size)
+        if not 0 < self.top_k <= L_MAX_TOPK or not 0 < self.max_boxes <= self.top_k:
+            raise ValueError(f"FrameDetector: need 0 < max_boxes <= top_k <= {L_MAX_TOPK}, got max_boxes {max_boxes}, top_k {top_k}")
+        if self.batch_size < 1:
+            raise ValueError(f"FrameDetector: batch_size must be positive, got {batch_size}")
+        self.outline = tuple(int(c) for c in outline)
+        if len(self.outline) != 3 or any(not 0 <= c <= 255 for c in self.outline):
+            raise ValueError(f"FrameDetector: outline must be one RGB triple of bytes, got {outline!r}")
+        self.bw = bool(model.get_bw())
+        self.width, self.height = (int(v) for v in model.img_size())
+
+    @property
+    def device(self):
+        return next(self.model.parameters()).device
+
+    # -- host half (worker thread): take a batch from the iterable, plan it, pack it into the slot's pinned buffer
+    def _stage(self, it, first, slot):
+        frames = [_check_frame(f, first + i) for i, f in enumerate(islice(it, self.batch_size))]
+        if not frames:
+            return None
+        plan = BatchPlan([(f.shape[1], f.shape[0]) for f in frames], self.width, self.height, self.top_k)
+        slot.pin_in = _pinned(slot.pin_in, plan.in_bytes)
+        plan.pack(slot.pin_in.numpy(), frames)
+        return plan, slot
+
+    # -- device half: copy, resize, forward, post-process, draw, copy back, ONE synchronisation
+    def _run(self, plan, slot, keep_on_device):
+        L = _lib.lib()
+        dev = self.device
+        B, K = plan.B, plan.K
+        with torch.cuda.device(dev), torch.no_grad():
+            st = torch.cuda.current_stream(dev)
+            dbuf = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
+            dbuf[:plan.in_bytes].copy_(slot.pin_in[:plan.in_bytes], non_blocking=True)
+            pool = dbuf[plan.pool_off:plan.pool_off + plan.pool_bytes]
+            host = slot.pin_in.numpy()
+            imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
+            self.model.eval()
+            det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k)
+            count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
+            base = dbuf.data_ptr()
+            L.check(L.detect_draw_boxes(host.ctypes.data + plan.det_off, base + plan.det_off, B, det.boxes.data_ptr(), count.data_ptr(), K,
+                                        base + plan.pool_off, plan.pool_bytes, *self.outline, base + plan.fb_off, base + plan.rect_off,
+                                        base + plan.skip_off, st.cuda_stream), "detect_draw_boxes")
+            dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(det.prob.reshape(-1))
+            dbuf[plan.count_off:plan.count_off + B * 4].view(torch.int32).copy_(count)
+            lo = plan.fb_off if keep_on_device else plan.pool_off
+            slot.pin_out = _pinned(slot.pin_out, plan.nbytes - lo)
+            slot.pin_out[:plan.nbytes - lo].copy_(dbuf[lo:plan.nbytes], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(st)
+            done.synchronize()                                   # the batch's one host synchronisation
+        out = slot.pin_out.numpy()
+
+        def table(off, nbytes, dtype, shape):
+            return out[off - lo:off - lo + nbytes].view(dtype).reshape(shape)
+        fb = table(plan.fb_off, B * K * 32, np.float64, (B, K, 4))
+        rects = table(plan.rect_off, B * K * 16, np.int32, (B, K, 4))
+        prob = table(plan.prob_off, B * K * 4, np.float32, (B, K))
+        cnt = table(plan.count_off, B * 4, np.int32, (B,))
+        skipped = table(plan.skip_off, B * 4, np.int32, (B,))
+        res = []
+        for b, (off, (w, h)) in enumerate(zip(plan.offsets, plan.sizes)):
+            n = min(int(cnt[b]), K)
+            if keep_on_device:
+                ann = pool[off:off + 3 * w * h].view(h, w, 3)
+            else:
+                at = plan.pool_off - lo + off
+                ann = out[at:at + 3 * w * h].reshape(h, w, 3).copy()         # the pinned buffer is the next batch's
+            res.append(FrameDetections(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann))
+        return res
+
+    def detect_frames(self, frames, keep_on_device=False):
+        """frames: any iterable of (H, W, 3) uint8 RGB arrays (sizes may differ inside a batch) -> yields one `FrameDetections` per frame, in
+        order.  keep_on_device: `annotated` is a device tensor (a view of the batch's device buffer) and no pixel is copied back."""
+        _lib.require_gpu()
+        it = iter(frames)
+        slots = [_Slot(), _Slot()]                               # this generator's own: several may be alive on one detector
+        stager = ThreadPoolExecutor(1, thread_name_prefix="mdcv-detect-stage")
+        try:
+            n, first = 0, 0
+            pending = stager.submit(self._stage, it, first, slots[0])
+            while True:
+                staged = pending.result()
+                if staged is None:
+                    break
+                n += 1
+                first += staged[0].B
+                pending = stager.submit(self._stage, it, first, slots[n % 2])     # packed while the device works on this batch
+                yield from self._run(*staged, keep_on_device)
+        finally:
+            stager.shutdown(wait=True, cancel_futures=True)
+
+
+# --------------------------------------------------------------------------------------------- the reference's two functions (detect.py)
+def _open_rgb(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode != "RGB":
+            raise ValueError(f"{path}: Pillow mode {im.mode!r} is not supported, only 'RGB' (the reference draws on the unconverted image, "
+                             f"where the ink of outline=\"red\" depends on the mode); convert the file to RGB first")
+        return np.asarray(im, dtype=np.uint8)
+
+
+def _save(annotated, path):
+    from PIL import Image
+    Image.fromarray(annotated).save(path)
+    return path
+
+
+def _detector(model, device, conf_thres, nms_thres, **kw):
+    """`device` is where the reference moves its input (detect.py:78) and where the caller has put the model (detect.py:51): the batches
+    are built on the model's device, so the two must be the same GPU.  None: the model's device."""
+    if device is not None:
+        want, have = torch.device(device), next(model.parameters()).device
+        if want.type != "cuda":
+            raise _lib.MdcvError(f"detect: device {device!r} is not a GPU; there is no CPU fallback")
+        if have.type != "cuda" or (want.index is not None and want.index != have.index):
+            raise ValueError(f"detect: device {device!r} is not the model's device {str(have)!r}; move the model there first, as the reference's main does")
+    return FrameDetector(model, conf_thres=conf_thres, nms_thres=nms_thres, **kw)
+
+
+def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres):
+    """detect.py:60-111 for one RGB image file: mode 'image' saves under `output_path` with the file's own name, any other mode saves over
+    `target_path` (the reference's rule for its dumped video frames); the saved path is returned.  With no detection the image is
+    saved unannotated.  `device` must be the GPU the model is on (or None).  Each call builds its own detector: for many files use `detect`
+    on their directory."""
+    frame = _open_rgb(target_path)
+    res = next(iter(_detector(model, device, conf_thres, nms_thres, batch_size=1).detect_frames([frame])))
+    if mode == "image":
+        return _save(res.annotated, os.path.join(output_path, target_path.split("/")[-1]))
+    return _save(res.annotated, target_path)
+
+
+def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16):
+    """detect.py:113-196.  An image file (.jpg / .jpeg / .png / .tif) goes through `single_img_detect`; a directory has its image files,
+    sorted by name, detected in batches of `batch_size` and written to `output_path` under their own names (-> the list of paths).
+    Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead."""
+    ext = os.path.splitext(target_path)[-1].lower()
+    if os.path.isdir(target_path):
+        names = sorted(f for f in os.listdir(target_path)
+                       if os.path.splitext(f)[-1].lower() in IMG_FORMATS and os.path.isfile(os.path.join(target_path, f)))
+        print(f"Detection Mode is: directory ({len(names)} images)")
+        det = _detector(model, device, conf_thres, nms_thres, batch_size=batch_size)
+        frames = (_open_rgb(os.path.join(target_path, f)) for f in names)
+        paths = [_save(res.annotated, os.path.join(output_path, f)) for f, res in zip(names, det.detect_frames(frames))]
+        print(f"Please check output images at {output_path}")
+        return paths
+    if ext in VID_FORMATS:
+        raise ValueError(f"{target_path}: video containers ({', '.join(VID_FORMATS)}) need cv2 to decode and encode, which this build does "
+                         f"not use; decode the frames yourself and pass them to mdcv.yolo.detect.FrameDetector.detect_frames, or dump them "
+                         f"to a directory and pass that")
+    if ext not in IMG_FORMATS:
+        raise ValueError(f"{target_path}: not an image file ({', '.join(IMG_FORMATS)}) or a directory")
+    print("Detection Mode is: image")
+    path = single_img_detect(target_path=target_path, output_path=output_path, mode="image", model=model, device=device,
+                             conf_thres=conf_thres, nms_thres=nms_thres)
+    print(f"Please check output image at {path}")
+    return path
