@@ -391,6 +391,60 @@ int mdcv_detect_draw_boxes(const long long* desc_host, const long long* desc, in
                            unsigned char* pool, long long pool_bytes, int red, int green, int blue, double* frame_boxes, int* rects,
                            int* skipped, void* stream);
 
+/* The same call without the outline: steps a to c only, through the same kernel, so frame_boxes, rects and skipped hold the same bytes as
+ * mdcv_detect_draw_boxes writes for the same arguments, and no byte of any pool is read or written (only pool_bytes is taken, for the same
+ * descriptor checks).  The cone pipeline maps first, cuts its crops out of the untouched frames (mdcv_crop_resize_frames_u8), and calls
+ * mdcv_detect_draw_boxes afterwards. */
+int mdcv_detect_map_boxes(const long long* desc_host, const long long* desc, int B, const float* boxes, const int* count, int K,
+                          long long pool_bytes, double* frame_boxes, int* rects, int* skipped, void* stream);
+
+/* ---- cone key points on whole frames, drawn on the device (csrc/kpt_detect.hip; RektNet/detect.py and RektNet/utils.py:61-66 for every
+ *      cone of every frame of a batch).  Frames and descriptors are mdcv_detect_draw_boxes': uint8 HWC RGB, rows of 3 * W bytes, at any
+ *      byte offset in `pool`; of a descriptor these calls read off, W, H (and test the pads' range), not the ratio.  desc_host is validated
+ *      (MDCV_EARG, nothing is enqueued); desc is its device copy, which the kernels check again.  One launch each; no state is kept.
+ *
+ *      mdcv_crop_resize_frames_u8: rects [B,K,4] int32 (x0, y0, x1, y1 as mdcv_detect_draw_boxes writes them) and count [B] are device
+ *      arrays the host never reads.  Slot k of frame b is looked at when k < min(count[b], K, max_per_frame).  Its window is the rect
+ *      clipped to the frame, both ends inclusive: cx0 = max(x0, 0), cx1 = min(x1, W - 1), cy0 = max(y0, 0), cy1 = min(y1, H - 1).  A box HAS
+ *      A CROP unless the window is empty (cx1 < cx0 or cy1 < cy0: the skipped rect (0, 0, -1, -1) among them), a side is above
+ *      MDCV_KPTLOAD_MAX_SIDE, or the frame's device descriptor fails its check.  The boxes with a crop are numbered m = 0, 1, ... in
+ *      (frame, slot) order by an exclusive prefix computed on the device, and for each:
+ *       crops  [m,3,S,S] fp32   mdcv_kptload_batch's image rule applied to the window's pixels read in place: cv2's 8-bit INTER_LINEAR to
+ *                               S x S, then (float)(u8 / 255.0); planes B, G, R (the pool is RGB: plane p is byte 2 - p of a pixel)
+ *       owner  [m,2]   int32    (b, k)
+ *       window [m,4]   int32    (cx0, cy0, w, h)
+ *      and total [1] int32 = their number.  crops / owner / window hold B * min(K, max_per_frame) rows; rows at total and beyond are not
+ *      written.  MDCV_KPTLOAD_MIN_SIZE <= S <= MDCV_KPTLOAD_MAX_SIZE, 1 <= B, K <= 65535, max_per_frame >= 1,
+ *      B * min(K, max_per_frame) <= 2^20, 1 <= pool_bytes <= 2^60, no null pointer.
+ *
+ *      mdcv_kpt_draw_points: pts [M,7,2] fp32 (x, y normalised in the window), window [M,4] and owner [M,2] as above (of owner only the
+ *      image index is read), all on the device; colours: 7 x 3 bytes ON THE HOST, (R, G, B) of key point 0..6, copied into the launch.
+ *       centers [M,7,2] int32   (wx0 + (int)((double)pt_x * w), wy0 + (int)((double)pt_y * h)): the product in IEEE double, truncated
+ *                               toward zero (what `int(pt[0] * w)` gave under NumPy 1.x, where float32 * int is a float64).  A point that
+ *                               is NaN or infinite or whose product has magnitude >= 2^30 is not drawn, gets (-1, -1), and skipped[image]
+ *                               counts it; so do all 7 points of a cone whose image index is outside [0, n_images) (not counted), whose
+ *                               image's device descriptor fails, or whose window does not lie inside its image (x0, y0 >= 0, w, h >= 1,
+ *                               x0 + w <= W, y0 + h <= H)
+ *       pool                    each drawn point as cv2.circle(img, c, 2, colour, -1) (LINE_8, shift 0): the 13 pixels |dx| + |dy| <= 2
+ *                               around the centre, clipped to the IMAGE (not the window).  Overlapping discs: a pixel holds the colour of
+ *                               the LAST point covering it in (row m, key point) order among the cones of its image, as after the
+ *                               reference's sequential loop, under any schedule; no other byte of the pool is written.
+ *      Rows of one image must be contiguous in owner (image-major, as mdcv_crop_resize_frames_u8 writes them): cones of one image in two
+ *      separate runs are ordered only inside each run.  skipped [n_images] is zeroed by the call (a memset on `stream`).  M == 0: only
+ *      that memset.  1 <= n_images <= 65535, 0 <= M <= 2^20.
+ *
+ *      mdcv_kpt_heatmap_mosaic: hm [B,7,S,S] fp32 -> out [B,7*S,S] uint8, the `_hm` picture of RektNet/detect.py:40-48.  Per map:
+ *      cmin, cmax of the map; v = (x - cmin) / (cmax - cmin), each a correctly rounded float32 operation; out = rint((double)v * 255.0),
+ *      ties to even, saturated to 0..255 (cv2.imwrite's convertTo(CV_8U) of the float64 array), NaN -> 0.  A constant map, and a map
+ *      holding a NaN, give zeros (a departure: the reference divides by zero).  0 <= B <= 65535, 1 <= S <= 4096. */
+int mdcv_crop_resize_frames_u8(const long long* desc_host, const long long* desc, int B, const unsigned char* pool, long long pool_bytes,
+                               const int* rects, const int* count, int K, int max_per_frame, int S, float* crops, int* owner, int* window,
+                               int* total, void* stream);
+int mdcv_kpt_draw_points(const long long* desc_host, const long long* desc, int n_images, unsigned char* pool, long long pool_bytes,
+                         const float* pts, const int* window, const int* owner, int M, const unsigned char* colours, int* centers,
+                         int* skipped, void* stream);
+int mdcv_kpt_heatmap_mosaic(const float* hm, int B, int S, unsigned char* out, void* stream);
+
 /* ---- optimizer step over the flat fp32 parameter buffer (train.py:180-187,72 ; train_eval.py:263,72) */
 int mdcv_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr, float beta1,
                    float beta2, float eps, float weight_decay, float grad_scale, void* stream);

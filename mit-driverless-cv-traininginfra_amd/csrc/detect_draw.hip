@@ -17,30 +17,15 @@
 // bytes only for the at most 3 + 3 bytes in front of and behind them.  The vertical edges are 3 bytes per row, a row pitch apart: byte
 // stores, one pixel per lane.  Plain vector stores only.  The launch is latency-sized (a box's outline is a few hundred bytes to a few KB):
 // 256 lanes cover the perimeter of a typical box in one or two trips; no LDS, no barrier, a handful of registers.
+// mdcv_detect_map_boxes runs steps a to c alone (the same kernel with `draw` off, so the same bytes in frame_boxes / rects / skipped): the
+// cone pipeline maps first, reads the crops out of the untouched frames, and draws afterwards (csrc/kpt_detect.hip).
 // Built with -ffp-contract=off like the other byte-exact units (the map is a division and a subtraction: nothing to contract, and kept so).
 #include "common.h"
-#include "../../include/mdcv_hip.h"
+#include "detect_desc.h"
 
 namespace {
 
 constexpr double kLimit = 1073741824.0;        // 2^30
-constexpr int kMaxSide = 1 << 24;
-
-enum { DD_OFF = 0, DD_W = 1, DD_H = 2, DD_RATIO = 3, DD_PAD_W = 4, DD_PAD_H = 5 };
-
-// a frame descriptor is good when its frame lies inside the pool (64-bit arithmetic) and its pads are ints
-__host__ __device__ inline bool detect_frame_ok(const long long* d, long long pool_bytes) {
-  const long long off = d[DD_OFF], W = d[DD_W], H = d[DD_H];
-  if (off < 0 || W < 1 || H < 1 || W > kMaxSide || H > kMaxSide) return false;
-  if (d[DD_PAD_W] < -kMaxSide || d[DD_PAD_W] > kMaxSide || d[DD_PAD_H] < -kMaxSide || d[DD_PAD_H] > kMaxSide) return false;
-  return off <= pool_bytes && 3 * W * H <= pool_bytes - off;
-}
-
-__host__ __device__ inline double desc_ratio(const long long* d) {
-  union { long long i; double f; } u;
-  u.i = d[DD_RATIO];
-  return u.f;
-}
 
 struct DrawArgs {
   const long long* desc;
@@ -53,6 +38,7 @@ struct DrawArgs {
   double* frame_boxes;
   int* rects;
   int* skipped;
+  int draw;                                      // 0: mdcv_detect_map_boxes, steps a to c only
 };
 
 struct Ink { unsigned c0, c1, c2, p0, p1, p2; };      // the three bytes, and the dword of a run at byte offsets 0, 1, 2 modulo 3
@@ -76,7 +62,7 @@ __global__ __launch_bounds__(256) void detect_draw_kernel(DrawArgs A) {
   const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   if (k >= A.count[b]) return;
   const long long* d = A.desc + (size_t)b * MDCV_DETECT_DESC;
-  const double ratio = desc_ratio(d);
+  const double ratio = detect_desc_ratio(d);
   const double pw = (double)d[DD_PAD_W], ph = (double)d[DD_PAD_H];
   const size_t slot = ((size_t)b * A.K + k) * 4;
   const float* bx = A.boxes + slot;
@@ -99,7 +85,7 @@ __global__ __launch_bounds__(256) void detect_draw_kernel(DrawArgs A) {
     if (!ok) atomicAdd(A.skipped + b, 1);                                 // integer: the total does not depend on the order
   }
   // the host entry validated its copy of the table; the device copy is checked again so that no descriptor can index outside the pool
-  if (!ok || !detect_frame_ok(d, A.pool_bytes)) return;
+  if (!A.draw || !ok || !detect_frame_ok(d, A.pool_bytes)) return;
   const int W = (int)d[DD_W], H = (int)d[DD_H];
   const size_t pitch = (size_t)3 * W;
   unsigned char* __restrict__ frame = A.pool + d[DD_OFF];
@@ -131,26 +117,38 @@ __global__ __launch_bounds__(256) void detect_draw_kernel(DrawArgs A) {
 
 extern "C" {
 
-int mdcv_detect_draw_boxes(const long long* desc_host, const long long* desc, int B, const float* boxes, const int* count, int K,
-                           unsigned char* pool, long long pool_bytes, int red, int green, int blue, double* frame_boxes, int* rects,
-                           int* skipped, void* stream) {
+// both entry points: the same checks, the same memset, the same kernel; `draw` == 0 stops a box after its tables are written
+static int map_or_draw(const long long* desc_host, const long long* desc, int B, const float* boxes, const int* count, int K,
+                       unsigned char* pool, long long pool_bytes, int red, int green, int blue, double* frame_boxes, int* rects,
+                       int* skipped, int draw, void* stream) {
   if (B < 0 || K < 0 || B > 65535 || K > 65535 || pool_bytes < 0 || pool_bytes > (1ll << 60)) return MDCV_EARG;
   if (red < 0 || red > 255 || green < 0 || green > 255 || blue < 0 || blue > 255) return MDCV_EARG;
   if (B == 0) return MDCV_OK;
-  if (!desc_host || !desc || !count || !skipped || (!pool && pool_bytes > 0)) return MDCV_EARG;
+  if (!desc_host || !desc || !count || !skipped || (draw && !pool && pool_bytes > 0)) return MDCV_EARG;
   if (K > 0 && (!boxes || !frame_boxes || !rects)) return MDCV_EARG;
   for (int b = 0; b < B; ++b) {
     const long long* d = desc_host + (size_t)b * MDCV_DETECT_DESC;
-    const double ratio = desc_ratio(d);
+    const double ratio = detect_desc_ratio(d);
     if (!detect_frame_ok(d, pool_bytes) || !(ratio > 0.0) || !(ratio < kLimit)) return MDCV_EARG;
   }
   if (K == 0) return MDCV_OK;                                            // nothing can be kept: nothing is launched or written
   hipError_t e = hipMemsetAsync(skipped, 0, (size_t)B * sizeof(int), (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
-  DrawArgs a{desc, boxes, count, K, pool, pool_bytes, (unsigned)red, (unsigned)green, (unsigned)blue, frame_boxes, rects, skipped};
+  DrawArgs a{desc, boxes, count, K, pool, pool_bytes, (unsigned)red, (unsigned)green, (unsigned)blue, frame_boxes, rects, skipped, draw};
   MDCV_LAUNCH(detect_draw_kernel, dim3((unsigned)K, (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
   MDCV_CHECK_LAUNCH();
   return MDCV_OK;
+}
+
+int mdcv_detect_draw_boxes(const long long* desc_host, const long long* desc, int B, const float* boxes, const int* count, int K,
+                           unsigned char* pool, long long pool_bytes, int red, int green, int blue, double* frame_boxes, int* rects,
+                           int* skipped, void* stream) {
+  return map_or_draw(desc_host, desc, B, boxes, count, K, pool, pool_bytes, red, green, blue, frame_boxes, rects, skipped, 1, stream);
+}
+
+int mdcv_detect_map_boxes(const long long* desc_host, const long long* desc, int B, const float* boxes, const int* count, int K,
+                          long long pool_bytes, double* frame_boxes, int* rects, int* skipped, void* stream) {
+  return map_or_draw(desc_host, desc, B, boxes, count, K, nullptr, pool_bytes, 0, 0, 0, frame_boxes, rects, skipped, 0, stream);
 }
 
 }  // extern "C"

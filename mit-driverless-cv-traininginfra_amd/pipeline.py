@@ -5,6 +5,7 @@ RektNet/detect.py:29-39 runs KeypointNet on one pre-cut cone image resized with 
 code that joins them.  Here the join is device-resident: eval-mode Darknet -> `detect_postprocess` (conf filter + NMS for the
 whole batch) -> `crop_resize` (one launch: every kept box is cut out of its frame and bilinearly resampled to the
 KeypointNet input size) -> one batched KeypointNet eval.  Only the number of crops is read back (it sizes the batch).
+For real decoded frames of any sizes, with `detect`'s boxes and the result drawn, see `mdcv.yolo.detect.FrameConeDetector`.
 """
 import torch
 

@@ -17,6 +17,9 @@ batches of decoded frames that stay on the device from the upload to the annotat
 with ONE host synchronisation per batch and none per box.  Two staging slots: batch n + 1 is taken from the iterable and packed (on a
 worker thread) while the device works on batch n.
 
+`FrameConeDetector` carries the same batches on to the key points of every cone (crops cut from the pool, one batched KeypointNet eval,
+outlines and key-point discs drawn on the device).
+
 `single_img_detect` and `detect` take the reference's argument lists, so a caller swaps the import.  Departures, all
 documented in DESIGN.md §19: a box Pillow would refuse (x1 < x0, y1 < y0) or C could not convert (NaN, inf, magnitude >= 2^30) is skipped
 and counted instead of raising; a file whose Pillow mode is not RGB raises ValueError (the reference draws on the unconverted image and
@@ -112,7 +115,7 @@ class FrameDetections:
 
 class _Slot:
     def __init__(self):
-        self.pin_in, self.pin_out = None, None
+        self.pin_in, self.pin_out, self.pin_total = None, None, None
 
 
 def _pinned(t, need):
@@ -223,6 +226,184 @@ class FrameDetector:
                 yield from self._run(*staged, keep_on_device)
         finally:
             stager.shutdown(wait=True, cancel_futures=True)
+
+
+# ------------------------------------------------------------------------------------ frames -> boxes -> crops -> key points, drawn
+# RektNet/utils.py:62's BGR triples reversed: the pool is RGB, so the picture shows the reference's colours
+KPT_COLOURS_RGB = ((0, 255, 0), (0, 0, 255), (0, 255, 255), (255, 255, 0), (255, 0, 255), (127, 255, 127), (127, 127, 255))
+NUM_KPT = 7
+
+
+def colour_table(colours):
+    """seven RGB triples -> the contiguous 7 x 3 uint8 table mdcv_kpt_draw_points takes (a host array)"""
+    t = np.ascontiguousarray(colours, dtype=np.int64)
+    if t.shape != (NUM_KPT, 3) or (t < 0).any() or (t > 255).any():
+        raise ValueError(f"key-point colours must be {NUM_KPT} RGB triples of bytes, got {colours!r}")
+    return np.ascontiguousarray(t, dtype=np.uint8)
+
+
+def padded_rows(M, bucket):
+    """rows of the key-point batch for M crops: the next multiple of `bucket` (as JointPipeline pads), 0 for none"""
+    return (M + bucket - 1) // bucket * bucket
+
+
+class ConeBatchPlan(BatchPlan):
+    """BatchPlan with the cone tables behind it: [total 1 i32] [owner cap,2 i32] [window cap,4 i32] [keypoints cap,7,2 f32]
+    [centers cap,7,2 i32] [skipped points B i32], cap = B * per rows, per = min(max_cones, K) crops per frame at most."""
+
+    def __init__(self, sizes, width, height, K, max_cones):
+        super().__init__(sizes, width, height, K)
+        self.per = min(int(max_cones), self.K)
+        self.cap = cap = self.B * self.per
+        self.total_off = self.nbytes
+        self.owner_off = self.total_off + 16
+        self.window_off = _align(self.owner_off + cap * 8)
+        self.pts_off = _align(self.window_off + cap * 16)
+        self.centers_off = _align(self.pts_off + cap * NUM_KPT * 8)
+        self.kskip_off = _align(self.centers_off + cap * NUM_KPT * 8)
+        self.nbytes = _align(self.kskip_off + self.B * 4)
+
+
+def scatter_cones(owner, pts, centers, b, n):
+    """the rows of frame b among a batch's cone tables (owner [M,2] = (frame, slot)) -> per-box arrays for its n boxes:
+    keypoints [n,7,2] float32 (NaN without a crop), keypoints_frame [n,7,2] int32 ((-1, -1) without), has_crop [n] bool"""
+    kp = np.full((n, NUM_KPT, 2), np.nan, np.float32)
+    kf = np.full((n, NUM_KPT, 2), -1, np.int32)
+    has = np.zeros(n, bool)
+    rows = np.nonzero(owner[:, 0] == b)[0]
+    slots = owner[rows, 1]
+    kp[slots], kf[slots], has[slots] = pts[rows], centers[rows], True
+    return kp, kf, has, rows
+
+
+class FrameCones(FrameDetections):
+    """One frame's result: FrameDetections' fields, and per box keypoints float32 [n,7,2] (x, y normalised in the crop; NaN for a box
+    without a crop), keypoints_frame int32 [n,7,2] (the disc centres as drawn, in frame pixels; (-1, -1) for a box without a crop or a
+    point that was skipped), has_crop bool [n], skipped_points (key points of this frame not drawn), and crops (float32 [c,3,S,S], the
+    KeypointNet inputs of the boxes with a crop in box order; None unless asked for)."""
+
+    __slots__ = ("keypoints", "keypoints_frame", "has_crop", "skipped_points", "crops")
+
+
+class FrameConeDetector(FrameDetector):
+    """`FrameConeDetector(model, keypoint_net).detect_frames(frames)`: FrameDetector's batches carried on to the key points of every cone,
+    everything between the upload and the annotated pixels on the device.  Per batch, on one stream: upload, pad-and-resize
+    from the pool, eval forward, `detect_postprocess`, the box mapping (`mdcv_detect_map_boxes`: FrameDetector's frame_boxes and rects,
+    no pixel touched), `mdcv_crop_resize_frames_u8` (every kept box's clipped window cut out of the untouched frame in the pool and resized
+    as RektNet's loaders resize, at most `max_cones` per frame), one batched `keypoint_net` eval on the crops, the box outlines
+    (`mdcv_detect_draw_boxes`), the key-point discs on top (`mdcv_kpt_draw_points`, `colours`: seven RGB triples), one D2H copy.
+
+    TWO host synchronisations per batch and none per box or cone: the crop total (it sizes the key-point batch, padded with zero rows to
+    a multiple of `bucket` as JointPipeline pads) and the end.  A batch without a crop skips the key-point forward.
+    `detect_frames(..., return_crops=True)` also copies the crops back (a third synchronisation; tests and debugging)."""
+
+    def __init__(self, model, keypoint_net, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
+                 max_cones=64, bucket=64, colours=KPT_COLOURS_RGB):
+        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size)
+        self.keypoint_net = keypoint_net
+        self.max_cones, self.bucket = int(max_cones), int(bucket)
+        if self.max_cones < 1 or self.bucket < 1:
+            raise ValueError(f"FrameConeDetector: max_cones and bucket must be positive, got {max_cones}, {bucket}")
+        size = tuple(int(v) for v in keypoint_net.image_size)
+        if size[0] != size[1] or not 16 <= size[0] <= 256:                    # MDCV_KPTLOAD_MIN_SIZE / MAX_SIZE
+            raise ValueError(f"FrameConeDetector: the key-point input must be square with a side in 16..256, got {size}")
+        if int(getattr(keypoint_net, "num_kpt", NUM_KPT)) != NUM_KPT:
+            raise ValueError(f"FrameConeDetector: the drawing kernel takes {NUM_KPT} key points per cone")
+        self.size = size[0]
+        self.colours = colour_table(colours)
+        self._return_crops = False
+
+    def _stage(self, it, first, slot):
+        frames = [_check_frame(f, first + i) for i, f in enumerate(islice(it, self.batch_size))]
+        if not frames:
+            return None
+        plan = ConeBatchPlan([(f.shape[1], f.shape[0]) for f in frames], self.width, self.height, self.top_k, self.max_cones)
+        slot.pin_in = _pinned(slot.pin_in, plan.in_bytes)
+        plan.pack(slot.pin_in.numpy(), frames)
+        return plan, slot
+
+    def _run(self, plan, slot, keep_on_device):
+        L = _lib.lib()
+        dev = self.device
+        B, K, S = plan.B, plan.K, self.size
+        with torch.cuda.device(dev), torch.no_grad():
+            st = torch.cuda.current_stream(dev)
+            dbuf = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
+            dbuf[:plan.in_bytes].copy_(slot.pin_in[:plan.in_bytes], non_blocking=True)
+            pool = dbuf[plan.pool_off:plan.pool_off + plan.pool_bytes]
+            host = slot.pin_in.numpy()
+            imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
+            self.model.eval()
+            det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k)
+            count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
+            base = dbuf.data_ptr()
+            desc_h, desc_d = host.ctypes.data + plan.det_off, base + plan.det_off
+            L.check(L.detect_map_boxes(desc_h, desc_d, B, det.boxes.data_ptr(), count.data_ptr(), K, plan.pool_bytes, base + plan.fb_off,
+                                       base + plan.rect_off, base + plan.skip_off, st.cuda_stream), "detect_map_boxes")
+            crops = torch.empty(max(padded_rows(plan.cap, self.bucket), 1), 3, S, S, dtype=torch.float32, device=dev)
+            L.check(L.crop_resize_frames_u8(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.rect_off, count.data_ptr(), K,
+                                            plan.per, S, crops.data_ptr(), base + plan.owner_off, base + plan.window_off,
+                                            base + plan.total_off, st.cuda_stream), "crop_resize_frames_u8")
+            if slot.pin_total is None:
+                slot.pin_total = torch.zeros(4, dtype=torch.int32, pin_memory=True)
+            slot.pin_total.copy_(dbuf[plan.total_off:plan.total_off + 16].view(torch.int32), non_blocking=True)
+            sized = torch.cuda.Event()
+            sized.record(st)
+            sized.synchronize()                                  # synchronisation 1 of 2: the crop total sizes the key-point batch
+            M = int(slot.pin_total.numpy()[0])
+            if M:
+                rows = padded_rows(M, self.bucket)
+                crops[M:rows].zero_()
+                self.keypoint_net.eval()
+                _hm, pts = self.keypoint_net(crops[:rows])
+                dbuf[plan.pts_off:plan.pts_off + M * NUM_KPT * 8].view(torch.float32).copy_(pts[:M].reshape(-1))
+            L.check(L.detect_draw_boxes(desc_h, desc_d, B, det.boxes.data_ptr(), count.data_ptr(), K, base + plan.pool_off, plan.pool_bytes,
+                                        *self.outline, base + plan.fb_off, base + plan.rect_off, base + plan.skip_off, st.cuda_stream),
+                    "detect_draw_boxes")
+            L.check(L.kpt_draw_points(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.pts_off, base + plan.window_off,
+                                      base + plan.owner_off, M, self.colours.ctypes.data, base + plan.centers_off, base + plan.kskip_off,
+                                      st.cuda_stream), "kpt_draw_points")
+            dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(det.prob.reshape(-1))
+            dbuf[plan.count_off:plan.count_off + B * 4].view(torch.int32).copy_(count)
+            lo = plan.fb_off if keep_on_device else plan.pool_off
+            slot.pin_out = _pinned(slot.pin_out, plan.nbytes - lo)
+            slot.pin_out[:plan.nbytes - lo].copy_(dbuf[lo:plan.nbytes], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(st)
+            done.synchronize()                                   # synchronisation 2 of 2
+            crops_host = crops[:M].cpu().numpy() if self._return_crops else None
+        out = slot.pin_out.numpy()
+
+        def table(off, nbytes, dtype, shape):
+            return out[off - lo:off - lo + nbytes].view(dtype).reshape(shape)
+        fb = table(plan.fb_off, B * K * 32, np.float64, (B, K, 4))
+        rects = table(plan.rect_off, B * K * 16, np.int32, (B, K, 4))
+        prob = table(plan.prob_off, B * K * 4, np.float32, (B, K))
+        cnt = table(plan.count_off, B * 4, np.int32, (B,))
+        skipped = table(plan.skip_off, B * 4, np.int32, (B,))
+        owner = table(plan.owner_off, M * 8, np.int32, (M, 2))
+        kpts = table(plan.pts_off, M * NUM_KPT * 8, np.float32, (M, NUM_KPT, 2))
+        centers = table(plan.centers_off, M * NUM_KPT * 8, np.int32, (M, NUM_KPT, 2))
+        kskip = table(plan.kskip_off, B * 4, np.int32, (B,))
+        res = []
+        for b, (off, (w, h)) in enumerate(zip(plan.offsets, plan.sizes)):
+            n = min(int(cnt[b]), K)
+            if keep_on_device:
+                ann = pool[off:off + 3 * w * h].view(h, w, 3)
+            else:
+                at = plan.pool_off - lo + off
+                ann = out[at:at + 3 * w * h].reshape(h, w, 3).copy()         # the pinned buffer is the next batch's
+            r = FrameCones(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann)
+            r.keypoints, r.keypoints_frame, r.has_crop, rows = scatter_cones(owner, kpts, centers, b, n)
+            r.skipped_points = int(kskip[b])
+            r.crops = crops_host[rows] if crops_host is not None else None
+            res.append(r)
+        return res
+
+    def detect_frames(self, frames, keep_on_device=False, return_crops=False):
+        """as FrameDetector.detect_frames -> yields one `FrameCones` per frame, in order"""
+        self._return_crops = bool(return_crops)
+        return super().detect_frames(frames, keep_on_device)
 
 
 # --------------------------------------------------------------------------------------------- the reference's two functions (detect.py)
