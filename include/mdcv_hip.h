@@ -346,6 +346,28 @@ int mdcv_imgload_aug_frames_batch(const int* desc_host, const int* desc, const l
                                   const unsigned char* pool, long long pool_bytes, int max_scr_w, int max_scr_h, int C, int H, int W,
                                   void* workspace, void* aug_workspace, float* out, void* stream);
 
+/* ---- the reference's four imgaug options on a finished detector batch (csrc/imgfx.hip; datasets.py:253-295: iaa.GaussianBlur,
+ *      iaa.AdditiveGaussianNoise(per_channel=0.5), iaa.SigmoidContrast, iaa.Sharpen of imgaug 0.3.0; DESIGN §16.3 defines the arithmetic).
+ *      src [B,3,H,W] fp32 holding u / 255 (what the entry points above write) -> dst, the same layout, out of place; one launch.  Per image
+ *      the ops run on the bytes in the order blur, noise, contrast, sharpen, each behind its flag; an image with no flag set is copied
+ *      bit for bit.  One descriptor of MDCV_IMGFX_DESC ints per image (mdcv/data/images.py writes them):
+ *       [0] blur      0 / 1     [1] r  radius, 1..7     [2..9]  the half table q[0..7], centre first: q >= 0, q[k] == 0 for k > r,
+ *                     q[0] + 2 * sum q[1..] == 256.  Separable, BORDER_REFLECT_101: t = sum q * src (unrounded), (sum q * t + 32768) >> 16
+ *       [10] noise    0 / 1     [11] per_channel  0: one draw per pixel shared by the channels, 1: one per (y, x, c)
+ *       [12] seed     32 bits   [13..14] scale, a double (low word first) in [0, 255].  Sample counter n = y * W + x, or 3 * n + c per
+ *                     channel; S = the twelve 16-bit halves of the six hash words of (seed, n, j) summed; the byte gets
+ *                     clip(rint(scale * (S - 393210) / 65536), -255, 255) added and is clipped to 0..255
+ *       [15] contrast 0 / 1     [16] table  index into `luts` (n_luts tables of 256 bytes, computed on the host), < n_luts
+ *       [17] sharpen  0 / 1     [18] kc  [19] kn  float32 bits of the centre and neighbour coefficients, kc in [0, 16], |kn| <= 2:
+ *                     rint((double)kc * centre + (double)kn * (sum of the 8 neighbours)) clipped to 0..255, BORDER_REFLECT_101
+ *       [20..23] must be 0
+ *      Every field is checked whether or not its flag is set, the table index only when [15] is.  fx_host is validated (MDCV_EARG, nothing
+ *      is enqueued); fx is its device copy, checked again by the kernel (an image whose device descriptor fails is written as zeros).
+ *      MDCV_EARG also for: C != 3, H or W < 16, H * W > 4096 * 4096, B outside 1..65535, dst overlapping src.  No scratch. */
+#define MDCV_IMGFX_DESC 24
+int mdcv_imgfx_batch(const int* fx_host, const int* fx, int B, const unsigned char* luts, int n_luts, int C, int H, int W, const float* src,
+                     float* dst, void* stream);
+
 /* ---- real key-point crop batches (csrc/kptload.hip; RektNet/dataset.py:34-56 ConeDataset.__getitem__ over RektNet/utils.py:73-96):
  *      B decoded crops (uint8, HWC, RGB, any height and width, packed back to back in `src` at unaligned byte offsets) ->
  *       images   [B,3,S,S] fp32: cv2.resize of the 8-bit crop to S x S with mdcv_crop_resize_u8's rule, then (float)(u8 / 255.0); the

@@ -2,7 +2,8 @@
 
 The host decodes (Pillow, on a thread pool) and crops each frame to the source window its output patch reads; everything from that
 uint8 window to the `[B,C,H,W]` fp32 batch runs in csrc/imgload.hip (two launches per batch) or, for a batch with an augmented sample,
-csrc/imgaug.hip (three or four).  What the reference's chain computes
+csrc/imgaug.hip (three or four), and one more launch of csrc/imgfx.hip for a batch with a blurred / noised / contrasted / sharpened
+sample.  What the reference's chain computes
 (CVC-YOLOv3/utils/datasets.py:124-315 with utils/utils.py's geometry and label helpers, torchvision 0.3's pad / resize / to_grayscale /
 hflip / to_tensor over Pillow) is reproduced exactly:
 
@@ -26,9 +27,19 @@ hflip / to_tensor over Pillow) is reproduced exactly:
   (`uniform(-0.04, 0.04)`) factors and the `shuffle` of the four ops; with `augment_affine or data_aug` the gate `random()` (`> 0`), angle
   `uniform(-10, 10)`, tx, ty `uniform(-40, 40)`, scale `uniform(0.9, 1.1)`, shear `uniform(-3, 3)`; then the flip.  A sample without boxes
   returns before all of this, as in the reference.  With the three options off no extra draw happens.
-
-Not supported (ValueError): the imgaug augmentations `blur`, `noise`, `contrast`, `sharpen`, `salt` (imgaug draws its noise from NumPy's
-generator; nothing available pins them).
+* the imgaug options (`blur`, `noise`, `contrast`, `sharpen`; datasets.py:253-295, imgaug 0.3.0 over OpenCV 4.1): `iaa.GaussianBlur`,
+  `iaa.AdditiveGaussianNoise(per_channel=0.5)`, `iaa.SigmoidContrast` and `iaa.Sharpen` on the 8-bit image behind the flip, in that
+  order.  Neither library can be pinned here, so DESIGN §16.3 defines the bytes: the blur is OpenCV's 8-bit fixed-point separable filter
+  with imgaug's kernel-size rule (cv2's own rounding is declared unpinned), the contrast imgaug's float32 256-entry table, the sharpen one
+  correctly rounded double expression over imgaug's float32 matrix, and the noise a counter-based integer generator of the same
+  distribution (imgaug draws from NumPy's global Mersenne stream, which no device reproduces: the distribution matches, not the stream).
+  Kernel tables, the contrast tables and the sharpen coefficients are computed here and shipped with the descriptors.  Draws continue the
+  sample's stream behind the flip in the reference's order: blur gate `random()` (`> 0.2`), `uniform(40, -40)` (drawn and discarded, as
+  the reference does), sigma `uniform(0, 3)`; noise gate (`> 0.3`), scale `uniform(0, 7.65)`; contrast gate (`> 0.5`), cutoff
+  `uniform(0.45, 0.75)`, gain `randint(5, 10)`; sharpen gate (`> 0.3`), alpha `uniform(0, 0.5)`.  imgaug's own draws (the per_channel coin
+  and the noise seed) come from a second generator, `random.Random(f"{seed}/{epoch}/{index}/imgaug")`.  With the four options off no
+  extra draw happens and no extra launch runs.  `salt` is accepted and ignored with a warning (the reference stores it and never reads
+  it); any of the four with `bw` raises ValueError (the reference then hands a 2-D array to `Image.fromarray(..., 'RGB')`).
 """
 import csv
 import json
@@ -51,7 +62,9 @@ AUG_DESC = 24                            # MDCV_IMGAUG_DESC
 FREF = 4                                 # MDCV_IMGLOAD_FREF
 STAGED = (-1, 0, 0, 0)                   # a frame reference that says: this image's window is in the staging buffer
 LANCZOS, BILINEAR = "lanczos", "bilinear"
-UNSUPPORTED = ("blur", "noise", "contrast", "sharpen", "salt")
+FX_DESC = 24                             # MDCV_IMGFX_DESC
+FX_MAX_R = 7                             # csrc/imgfx_desc.h IMGFX_MAX_R
+UNSUPPORTED = ()                         # every option of the reference's ImageLabelDataset is implemented
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3        # ColorJitter.get_params appends its four ops in this order
 _F32 = np.float32
 
@@ -367,6 +380,112 @@ def aug_descriptor(aug):
     return d
 
 
+# ------------------------------------------------------------------------------- blur / noise / contrast / sharpen (draws and tables)
+class ImageFx:
+    """One sample's imgaug parameters, each None when its op does not run.  blur: sigma; noise: (scale, per_channel, seed) with seed the
+    32 bits that key the device's counter-based generator; contrast: (gain, cutoff); sharpen: alpha."""
+
+    def __init__(self, blur=None, noise=None, contrast=None, sharpen=None):
+        self.blur = None if blur is None else float(blur)
+        self.noise = None if noise is None else (float(noise[0]), bool(noise[1]), int(noise[2]) & 0xffffffff)
+        self.contrast = None if contrast is None else (int(contrast[0]), float(contrast[1]))
+        self.sharpen = None if sharpen is None else float(sharpen)
+        if self.blur is not None and not (self.blur < 5.0 and blur_radius(self.blur) <= FX_MAX_R):
+            raise ValueError(f"blur sigma {self.blur}: sigma must stay below 5 (kernel radius {FX_MAX_R} at most; the reference draws it below 3)")
+        if self.noise is not None and not 0.0 <= self.noise[0] <= 255.0:
+            raise ValueError(f"noise scale {self.noise[0]} outside [0, 255]")
+        if self.sharpen is not None and not 0.0 <= self.sharpen <= 1.0:
+            raise ValueError(f"sharpen alpha {self.sharpen} outside [0, 1]")
+
+    def __bool__(self):
+        return any(v is not None for v in (self.blur, self.noise, self.contrast, self.sharpen))
+
+    def runs(self):
+        """some op changes bytes: a blur whose sigma imgaug skips does not"""
+        return (self.blur is not None and blur_radius(self.blur) > 0) or any(v is not None for v in (self.noise, self.contrast, self.sharpen))
+
+
+def draw_imgfx(rng, second, blur_on, noise_on, contrast_on, sharpen_on):
+    """The draws of datasets.py:253-295 from `rng`, in its order, unused ones included; `second()` -> the generator of imgaug's own
+    draws (the per_channel coin, then the noise seed), asked for only when the noise runs."""
+    blur = noise = contrast = sharpen = None
+    if blur_on and rng.random() > 0.2:
+        rng.uniform(40, -40)                                     # the reference's unused `angle`
+        blur = rng.uniform(0, 3.00)
+    if noise_on and rng.random() > 0.3:
+        scale = rng.uniform(0, 0.03 * 255)
+        r2 = second()
+        per_channel = r2.random() < 0.5                          # per_channel=0.5: a fair coin per image
+        noise = (scale, per_channel, r2.getrandbits(32))
+    if contrast_on and rng.random() > 0.5:
+        cutoff = rng.uniform(0.45, 0.75)
+        contrast = (rng.randint(5, 10), cutoff)
+    if sharpen_on and rng.random() > 0.3:
+        sharpen = rng.uniform(0, 0.5)
+    return ImageFx(blur, noise, contrast, sharpen)
+
+
+def blur_radius(sigma):
+    """imgaug 0.3.0 blur_gaussian_ (cv2 backend): 0 when the op is skipped, else the radius of its kernel size"""
+    if sigma <= 1e-3:
+        return 0
+    k = 3.3 * sigma if sigma < 3.0 else (2.9 * sigma if sigma < 5.0 else 2.6 * sigma)
+    k = int(max(k, 5))
+    return (k + 1 if k % 2 == 0 else k) // 2
+
+
+@lru_cache(maxsize=512)
+def blur_table(sigma):
+    """-> (r, half table q[0..r], centre first): the Gaussian in float64 normalised to sum 1, each tap floor(w * 256 + 0.5), the centre
+    corrected so that the whole kernel sums to 256 (OpenCV 4.1's 8-bit fixed point)"""
+    r = blur_radius(sigma)
+    w = [math.exp(-(i * i) / (2.0 * sigma * sigma)) for i in range(r + 1)]
+    total = w[0] + 2.0 * sum(w[1:])
+    q = [int(math.floor(v / total * 256.0 + 0.5)) for v in w]
+    q[0] = 256 - 2 * sum(q[1:])
+    return r, tuple(q)
+
+
+@lru_cache(maxsize=64)
+def sigmoid_table(gain, cutoff):
+    """imgaug 0.3.0 adjust_contrast_sigmoid's uint8 table, in its float32 arithmetic; the cast truncates"""
+    v = np.linspace(0, 1, 256, dtype=_F32)
+    table = 0 + 255 * 1 / (1 + np.exp(_F32(gain) * (_F32(cutoff) - v)))
+    return np.clip(table, 0, 255).astype(np.uint8)
+
+
+def sharpen_coefficients(alpha):
+    """imgaug 0.3.0 Sharpen's matrix at lightness 1: float32 arrays combined with the Python-float alpha -> (centre, neighbour) float32"""
+    nochange = np.array([[0, 0, 0], [0, 1, 0], [0, 0, 0]], dtype=_F32)
+    effect = np.array([[-1, -1, -1], [-1, 8 + 1, -1], [-1, -1, -1]], dtype=_F32)
+    m = (1 - alpha) * nochange + alpha * effect
+    assert m.dtype == _F32
+    return m[1, 1], m[0, 0]
+
+
+def fx_descriptor(fx, lut_index=0):
+    """MDCV_IMGFX_DESC ints for one image (include/mdcv_hip.h); `fx` None or empty, or an op that is off: the identity"""
+    d = np.zeros(FX_DESC, np.int32)
+    r, q, scale, kc, kn = 1, (256, 0), 0.0, _F32(1), _F32(0)
+    if fx is not None and fx.blur is not None and blur_radius(fx.blur) > 0:
+        r, q = blur_table(fx.blur)
+        d[0] = 1
+    if fx is not None and fx.noise is not None:
+        scale = fx.noise[0]
+        d[10], d[11] = 1, int(fx.noise[1])
+        d[12:13] = np.array([fx.noise[2]], np.uint32).view(np.int32)
+    if fx is not None and fx.contrast is not None:
+        d[15], d[16] = 1, lut_index
+    if fx is not None and fx.sharpen is not None:
+        kc, kn = sharpen_coefficients(fx.sharpen)
+        d[17] = 1
+    d[1] = r
+    d[2:2 + len(q)] = q
+    d[13:15] = np.array([scale], np.float64).view(np.int32)
+    d[18:20] = np.array([kc, kn], _F32).view(np.int32)
+    return d
+
+
 # ----------------------------------------------------------------------------------------------------------- labels (host, exact)
 def _t(a, b):            # a 0-dim float32 tensor meeting a Python number: the number is rounded to float32 first
     if isinstance(a, np.float32) or isinstance(b, np.float32):
@@ -487,7 +606,7 @@ def pack_layout(geoms, windows_nbytes, num_targets, frefs=None):
     """Byte layout of one batch's staging buffer: [descriptors][labels][coefficient tables][pixels], and behind them, only when a
     sample of the batch is augmented, [augmentation descriptors] (a batch without one is laid out exactly as before).  `frefs` (one
     frame reference per sample, `STAGED` for a staged one; a pooled sample's window has 0 bytes): the batch reads a frame cache, and
-    [frame references] come last."""
+    [frame references] follow.  Only when a sample has an imgaug op, [fx descriptors][contrast tables] come last."""
     p = _Packed()
     B = len(geoms)
     p.B, p.T = B, num_targets
@@ -506,6 +625,12 @@ def pack_layout(geoms, windows_nbytes, num_targets, frefs=None):
     if p.fref:
         p.fref_off = p.nbytes
         p.nbytes = _align(p.fref_off + B * FREF * 8)
+    p.fx = any(bool(getattr(g, "fx", None)) and g.fx.runs() for g in geoms)
+    if p.fx:
+        p.n_luts = sum(1 for g in geoms if getattr(g, "fx", None) and g.fx.contrast is not None)
+        p.fx_off = p.nbytes
+        p.lut_off = _align(p.fx_off + B * FX_DESC * 4)
+        p.nbytes = _align(p.lut_off + p.n_luts * 256)
     p.max_scr_w = max(g.desc[7] for g in geoms)
     p.max_scr_h = max(g.desc[8] for g in geoms)
     return p
@@ -535,6 +660,16 @@ def pack_batch(buf, p, geoms, windows, labels=None, frefs=None):
             aug[b] = aug_descriptor(getattr(g, "aug", None))
     if p.fref:
         buf[p.fref_off:p.fref_off + p.B * FREF * 8].view(np.int64).reshape(p.B, FREF)[:] = np.asarray(frefs, np.int64).reshape(p.B, FREF)
+    if p.fx:
+        fxd = buf[p.fx_off:p.fx_off + p.B * FX_DESC * 4].view(np.int32).reshape(p.B, FX_DESC)
+        luts = buf[p.lut_off:p.lut_off + p.n_luts * 256].reshape(p.n_luts, 256)
+        n = 0
+        for b, g in enumerate(geoms):
+            fx = getattr(g, "fx", None)
+            fxd[b] = fx_descriptor(fx, n)
+            if fx and fx.contrast is not None:
+                luts[n] = sigmoid_table(*fx.contrast)
+                n += 1
     if p.T and labels is not None:
         buf[p.lab_off:p.lab_off + p.B * p.T * 20].view(np.float32)[:] = np.asarray(labels, np.float32).reshape(-1)
 
@@ -542,7 +677,22 @@ def pack_batch(buf, p, geoms, windows, labels=None, frefs=None):
 def launch_batch(dev_buf, host_buf, p, channels, height, width, stream, pool=None):
     """Enqueue the kernels on `stream` for a staged batch already copied to `dev_buf` (device uint8) -> imgs [B,C,H,W]: the pair of
     csrc/imgload.hip, or csrc/imgaug.hip's sequence when the batch carries augmentation descriptors.  A batch with frame references
-    goes through the two `_frames_` entry points with `pool` (device uint8, or None): the same launches."""
+    goes through the two `_frames_` entry points with `pool` (device uint8, or None): the same launches.  A batch with fx descriptors
+    gets csrc/imgfx.hip's one launch behind them, out of place into a second batch buffer allocated here."""
+    imgs = _launch_load(dev_buf, host_buf, p, channels, height, width, stream, pool)
+    if not getattr(p, "fx", False):
+        return imgs
+    if channels != 3:
+        raise ValueError("blur / noise / contrast / sharpen need RGB batches (bw=False)")
+    out = torch.empty_like(imgs)
+    base, hb = dev_buf.data_ptr(), host_buf.ctypes.data
+    L = _lib.lib()
+    L.check(L.imgfx_batch(hb + p.fx_off, base + p.fx_off, p.B, base + p.lut_off if p.n_luts else None, p.n_luts, channels, height, width,
+                          imgs.data_ptr(), out.data_ptr(), stream.cuda_stream), "imgfx_batch")
+    return out
+
+
+def _launch_load(dev_buf, host_buf, p, channels, height, width, stream, pool):
     L = _lib.lib()
     dev = dev_buf.device
     imgs = torch.empty(p.B, channels, height, width, dtype=torch.float32, device=dev)
@@ -580,7 +730,7 @@ def launch_batch(dev_buf, host_buf, p, channels, height, width, stream, pool=Non
 
 def transform_batch(frames, geoms, bw=False, device=None, pool=None, offsets=None):
     """Synchronous convenience (tests, probes): decoded frames [(H, W, 3) uint8] + their geometries (each may carry `.aug`, an
-    `Augmentation` with its matrix set) -> imgs [B,C,H,W] fp32 on the device.  With `pool` (device uint8) and `offsets` (per sample: the
+    `Augmentation` with its matrix set, and `.fx`, an `ImageFx`) -> imgs [B,C,H,W] fp32 on the device.  With `pool` (device uint8) and `offsets` (per sample: the
     byte offset in `pool` at which its whole frame already lies, rows of 3 * frame width bytes; None: stage the window from `frames`),
     pooled samples are read in place and their entry of `frames` is not looked at."""
     _lib.require_gpu()
@@ -614,9 +764,11 @@ class ImageLabelBatches:
     `DataLoader(ImageLabelDataset(path, dataset_path, width, height, ..., num_images, bw, lr_flip, ts), batch_size, shuffle)` yields.
 
     `decode(path)` -> a PIL image or an (H, W, 3) uint8 array (default: `PIL.Image.open(path).convert('RGB')`), run on `num_workers`
-    threads.  `augment_hsv` / `augment_affine` / `data_aug` (both) turn on the reference's ColorJitter / affine augmentation.
-    `draws(epoch, index)` -> (patch_index, flip) or (patch_index, flip, aug) overrides the random draws (tests); `aug` is None, an
-    `Augmentation`, or a dict with `jitter` and / or `affine` in `Augmentation`'s form; when it is left out the augmentation stays as drawn.  `subset_seed` seeds the
+    threads.  `augment_hsv` / `augment_affine` / `data_aug` (both) turn on the reference's ColorJitter / affine augmentation, `blur` /
+    `noise` / `contrast` / `sharpen` its four imgaug options (not with `bw`); `salt` is accepted and ignored, as the reference ignores it.
+    `draws(epoch, index)` -> (patch_index, flip), (patch_index, flip, aug) or (patch_index, flip, aug, fx) overrides the random draws
+    (tests); `aug` is None, an `Augmentation`, or a dict with `jitter` and / or `affine` in `Augmentation`'s form; `fx` is None, an
+    `ImageFx`, or a dict with `blur`, `noise`, `contrast`, `sharpen` in `ImageFx`'s form; what is left out stays as drawn.  `subset_seed` seeds the
     `random.sample` of `num_images`; its default 0 is the `random.seed(0)` that CVC-YOLOv3/train.py:40 runs before it builds its
     loaders, so the training loader's subset is the one train.py draws.  `debug_mode` forces patch 0 as the reference does (the patch
     draw still happens first, so the flip draw is unchanged).  With `prefetch`, batch i+1 is decoded and
@@ -631,9 +783,14 @@ class ImageLabelBatches:
     def __init__(self, path, dataset_path, width, height, num_images=-1, bw=False, lr_flip=False, ts=True, batch_size=1, shuffle=True,
                  num_workers=None, seed=0, device=None, decode=None, ud_flip=False, subset_seed=0, draws=None, prefetch=True, debug_mode=False,
                  augment_hsv=False, augment_affine=False, data_aug=False, cache_bytes=None, **options):
-        bad = [k for k in UNSUPPORTED if options.pop(k, False)]
-        if bad:
-            raise ValueError(f"ImageLabelBatches does not implement {', '.join(bad)} (imgaug augmentations); set them False")
+        self.blur, self.noise, self.contrast, self.sharpen = (bool(options.pop(k, False)) for k in ("blur", "noise", "contrast", "sharpen"))
+        self.salt = options.pop("salt", False)                   # accepted and ignored: the reference stores it and never reads it
+        if self.salt:
+            warnings.warn("ImageLabelBatches: salt is ignored, as in the reference (ImageLabelDataset stores it and never reads it)")
+        self._fx_on = self.blur or self.noise or self.contrast or self.sharpen
+        if self._fx_on and bw:
+            raise ValueError("ImageLabelBatches: blur / noise / contrast / sharpen cannot be combined with bw (the reference builds an "
+                             "'RGB' image from the 2-D grayscale array there, which has no defined meaning)")
         for k in ("vis_batch", "upload_dataset", "n_cpu"):
             options.pop(k, None)
         if options:
@@ -685,8 +842,8 @@ class ImageLabelBatches:
         return idx
 
     def plan(self, index, epoch=0, frame_size=None):
-        """Host-only: the draws, geometry, augmentation (`.aug`: None or an `Augmentation` with its matrix) and labels of sample `index`
-        in `epoch` (frame_size: the decoded (W, H); default the CSV's)."""
+        """Host-only: the draws, geometry, augmentation (`.aug`: None or an `Augmentation` with its matrix; `.fx`: None or an `ImageFx`)
+        and labels of sample `index` in `epoch` (frame_size: the decoded (W, H); default the CSV's)."""
         w, h = frame_size if frame_size is not None else self.sizes[index]
         rng = random.Random(f"{self.seed}/{epoch}/{index}")
         patch = rng.randint(0, n_patches(w, h, self.scales[index], self.width, self.height) - 1) if self.ts else 0
@@ -697,6 +854,9 @@ class ImageLabelBatches:
         if boxed and (self.augment_hsv or self.augment_affine or self.data_aug):
             aug = draw_augmentation(rng, self.augment_hsv or self.data_aug, self.augment_affine or self.data_aug)
         flip = bool(self.lr_flip and boxed and rng.random() > 0.5)
+        fx = None
+        if boxed and self._fx_on:
+            fx = draw_imgfx(rng, lambda: random.Random(f"{self.seed}/{epoch}/{index}/imgaug"), self.blur, self.noise, self.contrast, self.sharpen)
         if self.draws is not None:
             d = self.draws(epoch, index)
             patch, flip = d[0], bool(d[1]) and boxed
@@ -704,11 +864,18 @@ class ImageLabelBatches:
                 aug = d[2] if boxed else None
                 if isinstance(aug, dict):
                     aug = Augmentation(aug.get("jitter"), aug.get("affine"))
+            if len(d) > 3:
+                fx = d[3] if boxed else None
+                if isinstance(fx, dict):
+                    fx = ImageFx(fx.get("blur"), fx.get("noise"), fx.get("contrast"), fx.get("sharpen"))
+                if fx and self.bw:
+                    raise ValueError("blur / noise / contrast / sharpen cannot be combined with bw")
         if aug is not None and aug.affine is not None:
             aug.matrix = inverse_affine_matrix(self.width, self.height, *aug.affine)
         g = sample_geometry(w, h, self.width, self.height, self.ts, self.scales[index] if self.ts else 1.0, patch, flip)
         g.index, g.uri = index, self.img_files[index]
         g.aug = aug if aug else None
+        g.fx = fx if fx else None
         g.labels = sample_labels(self.labels[index], g, self.num_targets_per_image, g.aug)
         return g
 

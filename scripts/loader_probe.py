@@ -9,6 +9,8 @@
 
 (e) the frame cache (`cache_bytes`): the step of (c) fed without the cache, in the cache's fill epoch and in hit epochs, beside
     SyntheticCones on the same lease; staged bytes per batch with and without; the hit-epoch loader alone (img/s, host ms per batch)
+(f) the blur / noise / contrast / sharpen launch (csrc/imgfx.hip) alone on a B=32 batch of 416x416: no flag (a copy), each op on
+    every image, all four on every image at the largest radius the reference draws, and the four as the loader draws them
 
 Device events after a warm-up, profiler off.  usage: loader_probe.py [files per format (default 32)] [parts, default abcd]"""
 import contextlib
@@ -293,8 +295,55 @@ def part_d(frames, repeats=5):
             print(f"        {name:32s} {1e3 * t.value:8.1f} us")
 
 
+def part_f(repeats=5):
+    print(f"(f) imgfx launch alone, B=32 of 416x416 RGB fp32 in and out, {2 * B * 3 * S * S * 4 / 1e6:.1f} MB read + written "
+          f"(ms per batch; {repeats} timings of 50 launches each, then the kernel's own time from one profiled launch)")
+    L = I._lib.lib()
+    src = (torch.randint(0, 256, (B, 3, S, S), device="cuda").float() / 255.0).contiguous()
+    dst = torch.empty_like(src)
+    st = torch.cuda.current_stream()
+
+    def drawn(b):
+        rng = random.Random(f"probe/{b}")
+        return I.draw_imgfx(rng, lambda: random.Random(f"probe/{b}/imgaug"), True, True, True, True)
+    rows = (("no flag (copy)", lambda b: None), ("blur sigma 1.0 (r 2)", lambda b: I.ImageFx(blur=1.0)),
+            ("blur sigma 2.99 (r 4)", lambda b: I.ImageFx(blur=2.99)), ("noise, per pixel", lambda b: I.ImageFx(noise=(4.0, False, b))),
+            ("noise, per channel", lambda b: I.ImageFx(noise=(4.0, True, b))), ("contrast", lambda b: I.ImageFx(contrast=(7, 0.6))),
+            ("sharpen", lambda b: I.ImageFx(sharpen=0.3)),
+            ("all four, r 4, per channel", lambda b: I.ImageFx(2.99, (4.0, True, b), (7, 0.6), 0.3)), ("as the loader draws them", drawn))
+    for name, make in rows:
+        fxs = [make(b) for b in range(B)]
+        desc, luts = [], []
+        for fx in fxs:
+            desc.append(I.fx_descriptor(fx, len(luts)))
+            if fx and fx.contrast is not None:
+                luts.append(I.sigmoid_table(*fx.contrast))
+        desc = np.stack(desc).astype(np.int32)
+        ddev = torch.from_numpy(desc).cuda()
+        ldev = torch.from_numpy(np.stack(luts)).cuda() if luts else None
+
+        def run():
+            L.check(L.imgfx_batch(desc.ctypes.data, ddev.data_ptr(), B, ldev.data_ptr() if ldev is not None else None, len(luts), 3, S, S,
+                                  src.data_ptr(), dst.data_ptr(), st.cuda_stream), "imgfx_batch")
+        ms = sorted(ev_ms(run, 50) for _ in range(repeats))
+        torch.cuda.synchronize()
+        L.profile_begin()
+        run()
+        torch.cuda.synchronize()
+        t = ctypes.c_float()
+        for i in range(L.profile_stop()):
+            L.profile_read(i, ctypes.byref(t), ctypes.create_string_buffer(256), 256)
+        flags = [sum(getattr(fx, k) is not None for fx in fxs if fx) for k in ("blur", "noise", "contrast", "sharpen")]
+        print(f"    {name:28s}: median {ms[len(ms) // 2]:7.3f} ms/batch  min {ms[0]:7.3f}  max {ms[-1]:7.3f}   kernel {1e3 * t.value:7.1f} us"
+              f"   images with blur / noise / contrast / sharpen: {flags}")
+
+
 def main():
     torch.cuda.set_device(0)
+    if "f" in PARTS:
+        part_f()
+    if not set(PARTS) & set("abcde"):
+        return
     frames = [frame(i) for i in range(8)]
     if "a" in PARTS:
         part_a(frames)
