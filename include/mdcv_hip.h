@@ -473,6 +473,26 @@ int mdcv_adam_step(float* params, const float* grads, float* exp_avg, float* exp
 int mdcv_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, int step, float lr, float momentum, float weight_decay,
                   float grad_scale, void* stream);
 
+/* ---- per-step bookkeeping of the training loops in one launch (csrc/train_log.hip; CVC-YOLOv3/train.py:54,63-64,74-90 ;
+ *      RektNet/train_eval.py:74-78): what the loops read back with `.item()` every step stays on the device.
+ *      losses: n_losses addresses ON THE HOST (copied into the launch), each a device pointer to ONE fp32 or NULL (= 0.0f: RektNet's
+ *      geometric loss without include_geo); 1 <= n_losses <= MDCV_TRAIN_LOG_MAX_LOSSES.
+ *      targets [B,T,5] fp32 on the device, read only if with_targets != 0.
+ *       count                   the number of (b, t) with MORE THAN ONE of targets[b,t,1:5] > 0 (train.py:63; NaN > 0 is false);
+ *                               0 if with_targets == 0 or B * T == 0
+ *       row [MDCV_TRAIN_LOG_ROW] fp32   loss_0 .. loss_{n-1}, (float)count, zeros to the end; every word of the row is written
+ *       acc [n_losses + 1] fp64         acc[j] += (double)loss_j for j < n_losses, then acc[n_losses] += (double)count + 1e-12: IEEE
+ *                               double additions by ONE thread, one launch after the other on the stream -- the sums Python's
+ *                               `epoch_losses[j] += loss.item()` and `epoch_num_targets += count + 1e-12` hold, bit for bit.  The caller
+ *                               starts acc[j] at 0.0 and acc[n_losses] at 1e-12 (train.py:54).
+ *      One workgroup: a strided pass over the B * T targets, an integer reduction (exact in any order), then the additions above.  Nothing
+ *      outside row[0 .. MDCV_TRAIN_LOG_ROW) and acc[0 .. n_losses] is written.  MDCV_EARG before any launch: losses, acc or row NULL, n_losses
+ *      out of range, B < 0, T < 0, B * T > INT_MAX, or with_targets != 0 and B * T > 0 and targets NULL. */
+#define MDCV_TRAIN_LOG_MAX_LOSSES 8
+#define MDCV_TRAIN_LOG_ROW 12
+int mdcv_train_log_step(const float* const* losses, int n_losses, const float* targets, int with_targets, int B, int T, double* acc,
+                        float* row, void* stream);
+
 /* ---- runtime plumbing: device query, HIP events on a caller stream, hipGraph capture of a launch sequence */
 int mdcv_device_info(int* cu_count, int* wave_size, long long* hbm_bytes, char* arch, int arch_len);
 int mdcv_event_create(void** ev);
