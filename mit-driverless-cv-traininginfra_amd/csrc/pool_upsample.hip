@@ -43,7 +43,9 @@ __global__ void upsample2x_bwd_kernel(const T* __restrict__ dout, int ldo, T* __
 
 // ---------------------------------------------------------------- 2x2 max-pool (yolo_baseline_tiny.cfg): stride 2, or stride 1 on a
 // bottom/right zero-padded input (nn.ZeroPad2d((0,1,0,1)) + nn.MaxPool2d(2,1), reference models.py:74-84).  idx = winning window
-// position (kh*2+kw; first maximum wins like torch; 4 = the zero padding won) so that backward is a pure gather.
+// position (kh*2+kw; first maximum wins like torch; 4 = the zero padding won) so that backward is a pure gather.  The update is torch's
+// `v > best || isnan(v)`: a NaN in a window reaches the output, and idx points at the LAST NaN in scan order (a real value never replaces a
+// NaN, a later NaN does).  The zero padding is never NaN.  A window of only -inf keeps idx = 0, whatever sits there.
 template <typename T>
 __global__ void maxpool2x2_fwd_kernel(const T* __restrict__ in, int ldi, T* __restrict__ out, int ldo, unsigned char* __restrict__ idx,
                                       int B, int H, int W, int C, int stride) {
@@ -66,7 +68,7 @@ __global__ void maxpool2x2_fwd_kernel(const T* __restrict__ in, int ldi, T* __re
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const float x = inside ? v[e] : 0.f;                    // zero padding takes part in the max
-        if (x > best[e]) { best[e] = x; bi[e] = inside ? (unsigned char)k : (unsigned char)4; }
+        if (x > best[e] || x != x) { best[e] = x; bi[e] = inside ? (unsigned char)k : (unsigned char)4; }
       }
     }
     *reinterpret_cast<uint4*>(out + op * ldo + cv * VEC) = ET<T>::pack(best);
@@ -105,8 +107,10 @@ __global__ void maxpool2x2_bwd_kernel(const T* __restrict__ dout, int ldo, const
 
 // ---------------------------------------------------------------- generic max-pool and nearest upsample (reference models.py:74-88 builds
 // nn.MaxPool2d(size, stride, (size - 1) // 2) and nn.Upsample(scale_factor = stride) for ANY size / stride; the bundled cfgs only use the
-// 2x2 pools and the x2 upsample above).  Padding never wins (-inf); the first maximum in (kh, kw) scan order wins like torch;
-// idx = kh*k + kw (k <= 15), so backward is a gather over the windows that contain the input pixel: no atomics, deterministic.
+// 2x2 pools and the x2 upsample above).  Padding never wins (-inf); the first maximum in (kh, kw) scan order wins like torch, and a NaN
+// beats everything but a later NaN (same update rule as above); idx = kh*k + kw (k <= 15), so backward is a gather over the windows that
+// contain the input pixel: no atomics, deterministic.  A window of only -inf keeps idx = 0, which may be a padding position: its gradient
+// goes nowhere.
 template <typename T>
 __global__ void maxpool_fwd_kernel(const T* __restrict__ in, int ldi, T* __restrict__ out, int ldo, unsigned char* __restrict__ idx,
                                    int B, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo) {
@@ -129,7 +133,7 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ in, int ldi, T* __restr
         ET<T>::unpack(*reinterpret_cast<const uint4*>(in + (((long long)b * H + h) * W + w) * ldi + cv * VEC), v);
 #pragma unroll
         for (int e = 0; e < VEC; ++e)
-          if (v[e] > best[e]) { best[e] = v[e]; bi[e] = (unsigned char)(kh * k + kw); }
+          if (v[e] > best[e] || v[e] != v[e]) { best[e] = v[e]; bi[e] = (unsigned char)(kh * k + kw); }
       }
     }
     *reinterpret_cast<uint4*>(out + op * ldo + cv * VEC) = ET<T>::pack(best);
