@@ -420,6 +420,35 @@ int mdcv_detect_draw_boxes(const long long* desc_host, const long long* desc, in
 int mdcv_detect_map_boxes(const long long* desc_host, const long long* desc, int B, const float* boxes, const int* count, int K,
                           long long pool_bytes, double* frame_boxes, int* rects, int* skipped, void* stream);
 
+/* ---- tile-and-scale inference, the join (csrc/detect_tiles.hip; mdcv/yolo/detect.py TiledFrameDetector).  Training cuts every scaled frame
+ *      into network-sized tiles (ts=True); inference on the same tiles yields, per frame, T tiles x K boxes in TILE coordinates.  This call
+ *      makes them one list per frame in scaled-frame coordinates and removes the duplicates of overlapping tiles.  The reference has no tiled
+ *      inference: the scan is its utils/nms.py:31-61 with the fp32 arithmetic of mdcv_nms / mdcv_detect_post (one shared device function), the
+ *      seam rule below is a departure.  ONE launch per batch of frames, one workgroup per frame, no workspace, no state between calls; the
+ *      counts are read on the device only.
+ *      tile_boxes [T,K,4] fp32, tile_prob [T,K] fp32, tile_count [T] int32: device arrays as mdcv_detect_post writes out_boxes, out_prob and
+ *      out_count for T tiles with K = its top_k (a count is clamped to 0..K).  Tile table: MDCV_TILE_DESC int32 words per tile,
+ *       [0] frame index in 0..B-1   [1] off_x   [2] off_y   [3] 0
+ *      the tiles of one frame contiguous, frames ascending (a frame may have none: count 0).  tiles_host is validated (MDCV_EARG, nothing is
+ *      enqueued); tiles is its device copy, which the kernel checks again per frame (a frame whose tiles fail gets count 0).
+ *      Per frame b:  candidates (t, k), k < tile_count[t], corner j = (float)((double)tile_boxes[t,k,j] + (double)off) (off_x for j = 0, 2, off_y
+ *      for j = 1, 3: one rounding), score tile_prob[t,k].  Visiting order: descending score, equal scores by ascending tile index, then
+ *      ascending slot; only the first top_k candidates in that order are considered (nms.py:26).  Greedy scan: a remaining candidate j stays
+ *      behind a kept i iff IoU <= overlap (a NaN leaves) and, when contain_thres >= 0 and j and i come from different tiles, also
+ *      inter / min(area_j, area_i) <= contain_thres -- the seam rule: it removes the part of a cone that a tile edge cut off when the
+ *      neighbouring tile holds the whole cone, which plain IoU cannot.  A negative contain_thres turns it off.
+ *      out_boxes [B,top_k,4] fp32, out_prob [B,top_k] fp32, out_src [B,top_k,2] int32 = (tile index in the batch, slot in the tile),
+ *      out_count [B] int32: kept boxes in visiting order; slots past out_count[b] hold zeros, their out_src (-1, -1).
+ *      Limits (beyond them MDCV_EARG): at most MDCV_TILE_MAX_PER_FRAME tiles per frame, K and top_k <= MDCV_NMS_MAX_TOPK (so at most 32768
+ *      candidates per frame), 1 <= top_k, |off| <= MDCV_TILE_MAX_OFFSET, B <= 65535.  B == 0, T == 0 or K == 0: MDCV_OK, nothing is enqueued
+ *      or written. */
+#define MDCV_TILE_DESC 4
+#define MDCV_TILE_MAX_PER_FRAME 64
+#define MDCV_TILE_MAX_OFFSET 16777216
+int mdcv_detect_merge_tiles(const float* tile_boxes, const float* tile_prob, const int* tile_count, const int* tiles_host, const int* tiles,
+                            int T, int K, int B, float overlap, float contain_thres, int top_k, float* out_boxes, float* out_prob,
+                            int* out_src, int* out_count, void* stream);
+
 /* ---- cone key points on whole frames, drawn on the device (csrc/kpt_detect.hip; RektNet/detect.py and RektNet/utils.py:61-66 for every
  *      cone of every frame of a batch).  Frames and descriptors are mdcv_detect_draw_boxes': uint8 HWC RGB, rows of 3 * W bytes, at any
  *      byte offset in `pool`; of a descriptor these calls read off, W, H (and test the pads' range), not the ratio.  desc_host is validated

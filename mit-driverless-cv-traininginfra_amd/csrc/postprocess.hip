@@ -14,8 +14,7 @@
 // -> a single-wave greedy scan that resolves each 64-candidate word in registers (v_readlane, no LDS round trip per
 // candidate) -> label matching and the AP integral (parallel prefix / envelope, ordered float32 sum).
 #include "common.h"
-
-#define MDCV_NMS_MAX_TOPK 512
+#include "nms_core.h"  // keys, PostSmem, radix select, rank sort, the pair arithmetic (and nms_scan.inc, the greedy scan): shared with detect_tiles.hip
 #ifdef MDCV_POST_TS   /* phase timestamps of workgroup 0 (scripts/post_phases.sh); never defined in the shipped build */
 #include <cstdio>
 __device__ long long g_post_ts[16];
@@ -26,18 +25,8 @@ __device__ long long g_post_ts[16];
 
 namespace {
 
-constexpr int KMAX = MDCV_NMS_MAX_TOPK;
-constexpr int KW = KMAX / 64;
-constexpr int PB = 1024;  // threads per image workgroup
-static_assert(PB == 2 * KMAX, "rank_sort_desc uses two threads per key");
 constexpr int CNT_STRIDE = 32;  // ints between per-image counters: one 128-byte line each
 constexpr int FILTER_ROWS = 1024;  // prediction rows per stage-1 workgroup
-
-__device__ __forceinline__ unsigned ord32(float f) {  // monotone float -> uint (NaN with sign 0 sorts highest)
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long make_key(float score, unsigned idx) { return ((unsigned long long)ord32(score) << 32) | idx; }
 
 // ---------------------------------------------------------------- stage 1
 // 256 threads x 4 rows; slots are allocated wave -> workgroup (LDS) -> one global atomic per workgroup, so the
@@ -101,60 +90,6 @@ struct PostArgs {
   float* out_boxes; float* out_prob; int* out_cls; long long* out_index; unsigned char* out_correct; int* out_count; float* out_stats;
 };
 
-struct PostSmem {
-  unsigned long long key[KMAX];
-  float4 box[KMAX];
-  float area[KMAX];
-  unsigned long long mask[KMAX][KW];
-  unsigned hist[256];
-  int keep[KMAX];
-  unsigned long long thresh;
-  int need, sel, count, ngt, done;
-  int wsum[PB / 64];
-};
-
-// top_k-th largest key of keys[0..cnt) (all keys distinct): MSB-first radix select, 8 bits a pass.
-// Returns a threshold t such that exactly `top_k` keys are >= t.
-__device__ unsigned long long radix_select(const unsigned long long* __restrict__ keys, int cnt, int top_k, PostSmem& sm) {
-  const int tid = threadIdx.x;
-  if (tid == 0) { sm.thresh = 0; sm.need = top_k; sm.done = 0; }
-  for (int p = 7; p >= 0; --p) {
-    if (tid < 256) sm.hist[tid] = 0;
-    __syncthreads();
-    const unsigned long long prefix = sm.thresh;
-    const int sh = 8 * p;
-    for (int i = tid; i < cnt; i += PB) {
-      const unsigned long long k = keys[i];
-      const bool match = (p == 7) || ((k >> (sh + 8)) == (prefix >> (sh + 8)));
-      if (match) atomicAdd(&sm.hist[(unsigned)(k >> sh) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {  // wave 0: suffix scan over 256 bins, 4 per lane, highest bins in the highest lane
-      const unsigned h0 = sm.hist[4 * tid], h1 = sm.hist[4 * tid + 1], h2 = sm.hist[4 * tid + 2], h3 = sm.hist[4 * tid + 3];
-      const unsigned s = h0 + h1 + h2 + h3;
-      unsigned incl = s;  // inclusive suffix sum over lanes >= tid
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_down(incl, o, 64);
-        if (tid + o < 64) incl += v;
-      }
-      const unsigned above = incl - s;
-      const unsigned need = (unsigned)sm.need;
-      if (above < need && need <= incl) {
-        unsigned a = above; int d; unsigned hd;
-        if (a + h3 >= need) { d = 3; hd = h3; }
-        else { a += h3; if (a + h2 >= need) { d = 2; hd = h2; } else { a += h2; if (a + h1 >= need) { d = 1; hd = h1; } else { a += h1; d = 0; hd = h0; } } }
-        sm.thresh = prefix | ((unsigned long long)(4 * tid + d) << sh);
-        sm.need = (int)(need - a);
-        sm.done = (hd == need - a);  // the whole bin is taken: lower bits of the threshold stay 0
-      }
-    }
-    __syncthreads();
-    if (sm.done) break;
-  }
-  return sm.thresh;
-}
-
 // AP / recall / precision (utils.py:58-119) of `count` (1..KMAX) detections already in confidence order; tp01[c] is 1.f
 // for a true positive.  Called by every thread of the workgroup; the result is valid on thread 0.
 // The cumulative counts are integers (prefix popcount), the precision envelope is a suffix maximum (exact in any
@@ -198,27 +133,6 @@ __device__ float4 ap_integral(PostSmem& sm, const float* tp01, int count, int ng
   return make_float4(ap, tpc / fn, tpc / (tpc + fpc), 1.f);
 }
 
-// descending sort of the distinct keys sm.key[0..K), K <= KMAX: rank = number of larger keys.  Two threads per key,
-// each counting over half of the others (the inner read is a wave-wide LDS broadcast).
-__device__ void rank_sort_desc(PostSmem& sm, int K) {
-  const int i = threadIdx.x & (KMAX - 1), h = threadIdx.x / KMAX;  // PB == 2 * KMAX
-  const int half = (K + 1) >> 1;
-  unsigned long long mine = 0;
-  int rank = 0;
-  if (i < K) {
-    mine = sm.key[i];
-    const int j0 = h * half, j1 = (j0 + half) < K ? (j0 + half) : K;
-#pragma unroll 8
-    for (int j = j0; j < j1; ++j) rank += sm.key[j] > mine ? 1 : 0;
-  }
-  if (h == 1 && i < K) sm.keep[i] = rank;
-  __syncthreads();
-  if (h == 0 && i < K) rank += sm.keep[i];
-  __syncthreads();
-  if (h == 0 && i < K) sm.key[rank] = mine;
-  __syncthreads();
-}
-
 template <bool BATCHED>
 __global__ __launch_bounds__(PB) void post_image_kernel(PostArgs A) {
   __shared__ PostSmem sm;
@@ -231,7 +145,7 @@ __global__ __launch_bounds__(PB) void post_image_kernel(PostArgs A) {
   TS(0);
   // ---- candidates -> sm.key[0..K) sorted by descending key
   unsigned long long thresh = 0;
-  if (cnt > A.top_k) thresh = radix_select(keys, cnt, A.top_k, sm);
+  if (cnt > A.top_k) thresh = radix_select([keys](int i) { return keys[i]; }, cnt, A.top_k, sm);
   TS(1);
   if (tid == 0) sm.sel = 0;
   __syncthreads();
@@ -280,12 +194,8 @@ __global__ __launch_bounds__(PB) void post_image_kernel(PostArgs A) {
       const int j = w * 64 + lane;
       bool rem = false;
       if (j > i && j < K) {
-        const float4 bj = sm.box[j];
-        const float xx1 = fmaxf(bj.x, bi.x), yy1 = fmaxf(bj.y, bi.y), xx2 = fminf(bj.z, bi.z), yy2 = fminf(bj.w, bi.w);
-        const float ww = fmaxf(xx2 - xx1, 0.f), hh = fmaxf(yy2 - yy1, 0.f);
-        const float inter = ww * hh;
-        const float uni = (sm.area[j] - inter) + ai;  // nms.py:56
-        const float iou = inter / uni;
+        float inter;
+        const float iou = nms_pair_iou(bi, ai, sm.box[j], sm.area[j], inter);
         rem = !(iou <= A.nms_thres);                  // survivors are IoU.le(overlap); NaN is removed
       }
       const unsigned long long m = __ballot(rem);
@@ -295,36 +205,9 @@ __global__ __launch_bounds__(PB) void post_image_kernel(PostArgs A) {
   __syncthreads();
 
   TS(5);
-  // ---- greedy scan, wave 0: lane w owns word w of the removed set.  Each 64-candidate word is resolved in
-  // registers: lane l holds row (64w + l)'s bits for this word, the walk over the 64 bits is scalar (v_readlane).
+  // ---- greedy scan, wave 0 (nms_scan.inc)
   if (wave == 0) {
-    unsigned long long removed = 0;
-    int count = 0;
-    const int Ku = __builtin_amdgcn_readfirstlane(K);
-    for (int w = 0; w < W; ++w) {
-      const int il = w * 64 + lane;
-      const unsigned long long diag = il < Ku ? sm.mask[il][w] : 0ull;
-      const int dlo = (int)(unsigned)diag, dhi = (int)(unsigned)(diag >> 32);
-      unsigned long long cur = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(removed >> 32), w) << 32) |
-                               (unsigned)__builtin_amdgcn_readlane((int)(unsigned)removed, w);
-      const int nb = Ku - w * 64;
-      if (nb < 64) cur |= ~0ull << nb;  // past the last candidate
-      unsigned long long kept = 0;
-#pragma unroll
-      for (int t = 0; t < 64; ++t) {
-        const unsigned long long row = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi, t) << 32) | (unsigned)__builtin_amdgcn_readlane(dlo, t);
-        const unsigned long long alive = ((cur >> t) & 1ull) - 1ull;  // all ones while candidate t has not been removed
-        kept |= (1ull << t) & alive;
-        cur |= row & alive;
-      }
-      if ((kept >> lane) & 1ull) sm.keep[count + __popcll(kept & ((1ull << lane) - 1))] = il;
-      count += __popcll(kept);
-      if (w + 1 < W && lane > w && lane < W) {  // rows of the kept candidates -> later words; all 64 reads in flight at once
-#pragma unroll
-        for (int t = 0; t < 64; ++t) removed |= sm.mask[w * 64 + t][lane] & (0ull - ((kept >> t) & 1ull));
-      }
-    }
-    if (lane == 0) sm.count = count;
+#include "nms_scan.inc"
   }
   __syncthreads();
   TS(6);

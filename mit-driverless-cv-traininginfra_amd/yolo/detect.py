@@ -20,6 +20,9 @@ worker thread) while the device works on batch n.
 `FrameConeDetector` carries the same batches on to the key points of every cone (crops cut from the pool, one batched KeypointNet eval,
 outlines and key-point discs drawn on the device).
 
+`TiledFrameDetector` / `TiledFrameConeDetector` run the same interface on the tiles training sees (`ts=True`): every tile at its native
+scale through the network, the tiles' detections merged per frame by `mdcv_detect_merge_tiles` (csrc/detect_tiles.hip).
+
 `single_img_detect` and `detect` take the reference's argument lists, so a caller swaps the import.  Departures, all
 documented in DESIGN.md §19: a box Pillow would refuse (x1 < x0, y1 < y0) or C could not convert (NaN, inf, magnitude >= 2^30) is skipped
 and counted instead of raising; a file whose Pillow mode is not RGB raises ValueError (the reference draws on the unconverted image and
@@ -67,18 +70,19 @@ def detect_descriptors(geoms, offsets):
 class BatchPlan:
     """Byte layout of one batch.  Device buffer: [resize descriptors, tables and frame references (images.pack_layout)] [detect
     descriptors] [pool: the whole frames] [frame_boxes B,K,4 f64] [rects B,K,4 i32] [prob B,K f32] [count B i32] [skipped B i32];
-    the pinned input is everything up to the end of the pool, the copy back is everything from the pool (or from the tables) on."""
+    the pinned input is everything up to the end of the pool, the copy back is everything from the pool (or from the tables) on.
+    Subclasses choose the resize samples (`_samples`) and may put input tables behind the detect descriptors (`_tables`)."""
+
+    src_off = None                           # tiled plans: [src B,K,2 i32] behind the tables
 
     def __init__(self, sizes, width, height, K):
         B = len(sizes)
         self.B, self.K, self.sizes = B, int(K), [(int(w), int(h)) for w, h in sizes]
-        self.geoms = [I.sample_geometry(w, h, width, height, ts=False) for w, h in self.sizes]
         self.offsets, self.pool_bytes = frame_offsets(self.sizes)
-        self.frefs = [I.frame_reference(g, o) for g, o in zip(self.geoms, self.offsets)]
-        self.layout = I.pack_layout(self.geoms, [0] * B, 0, self.frefs)
-        self.desc = detect_descriptors(self.geoms, self.offsets)
+        self._samples(width, height)
+        self.layout = I.pack_layout(self.geoms, [0] * len(self.geoms), 0, self.frefs)
         self.det_off = self.layout.nbytes
-        self.pool_off = _align(self.det_off + B * DETECT_DESC * 8)
+        self.pool_off = _align(self._tables(self.det_off + B * DETECT_DESC * 8))
         self.in_bytes = self.pool_off + self.pool_bytes
         self.fb_off = self.in_bytes                                          # 16-byte aligned: pool_off and pool_bytes both are
         self.rect_off = self.fb_off + B * self.K * 32
@@ -87,12 +91,88 @@ class BatchPlan:
         self.skip_off = _align(self.count_off + B * 4)
         self.nbytes = _align(self.skip_off + B * 4)
 
+    def _samples(self, width, height):
+        """the resize samples of the batch (geoms, frefs: one per network input) and the detect descriptors (one per frame)"""
+        self.geoms = [I.sample_geometry(w, h, width, height, ts=False) for w, h in self.sizes]
+        self.frefs = [I.frame_reference(g, o) for g, o in zip(self.geoms, self.offsets)]
+        self.desc = detect_descriptors(self.geoms, self.offsets)
+
+    def _tables(self, at):
+        """input tables behind the detect descriptors, which end at byte `at` -> where they end"""
+        return at
+
+    def _pack_tables(self, host):
+        pass
+
     def pack(self, host, frames):
         """fill the pinned input (uint8 numpy, >= in_bytes) with the batch"""
-        I.pack_batch(host, self.layout, self.geoms, [None] * self.B, frefs=self.frefs)
+        I.pack_batch(host, self.layout, self.geoms, [None] * len(self.geoms), frefs=self.frefs)
         host[self.det_off:self.det_off + self.desc.nbytes].view(np.int64)[:] = self.desc.reshape(-1)
+        self._pack_tables(host)
         for f, off, (w, h) in zip(frames, self.offsets, self.sizes):
             host[self.pool_off + off:self.pool_off + off + 3 * w * h] = f.reshape(-1)
+
+
+TILE_DESC = 4                            # MDCV_TILE_DESC
+MAX_TILES_PER_FRAME = 64                 # MDCV_TILE_MAX_PER_FRAME
+
+
+def tiled_descriptors(sizes, offsets, scales):
+    """MDCV_DETECT_DESC long longs per frame for tile-and-scale inference: a merged box is in scaled-frame pixels, so `ratio` is the
+    frame's scale (its float64 bits) and both pads are 0 -- mdcv_detect_map_boxes / _draw_boxes then compute x / scale, the inverse of
+    the training labels' scale_labels step"""
+    d = np.zeros((len(sizes), DETECT_DESC), np.int64)
+    for b, ((w, h), off, s) in enumerate(zip(sizes, offsets, scales)):
+        d[b, 0], d[b, 1], d[b, 2] = off, w, h
+        d[b, 3] = np.array([s], np.float64).view(np.int64)[0]
+    return d
+
+
+class TiledBatchPlan(BatchPlan):
+    """BatchPlan for tile-and-scale inference: frame b is scaled by scales[b] and cut into its `n_patches` network-sized tiles, exactly
+    the `sample_geometry(ts=True)` patches training sees.  Every tile is one resize sample with a frame reference into the batch's pool
+    (the tiles are resized from the pool bytes in place, nothing is staged twice).  Behind the detect descriptors lies the tile table
+    of mdcv_detect_merge_tiles, TILE_DESC int32 per tile: (frame, off_x, off_y, 0) with off = the rounded patch origin minus the
+    border, the same rounding `sample_geometry` applies; behind the output tables, [src B,K,2 i32].  `first`: the index of the
+    batch's first frame in the caller's sequence, for error messages."""
+
+    def __init__(self, sizes, width, height, K, scales, first=0):
+        self.scales = [float(s) for s in scales]
+        if len(self.scales) != len(sizes):
+            raise ValueError(f"TiledBatchPlan: {len(sizes)} frames but {len(self.scales)} scales")
+        self.first = int(first)
+        super().__init__(sizes, width, height, K)
+        self.src_off = self.nbytes
+        self.nbytes = _align(self.src_off + self.B * self.K * 8)
+
+    def _samples(self, width, height):
+        self.geoms, self.frefs, self.tile_frame, table = [], [], [], []
+        for b, ((w, h), s, off) in enumerate(zip(self.sizes, self.scales, self.offsets)):
+            try:
+                if not 0.0 < s < float(1 << 30):
+                    raise ValueError(f"scale must be positive and below 2^30, got {s}")
+                tiles = [I.sample_geometry(w, h, width, height, ts=True, scale=s)]
+                n = tiles[0].n_patches
+                if n > MAX_TILES_PER_FRAME:
+                    raise ValueError(f"scale {s} cuts a {w}x{h} frame into {n} tiles of {width}x{height}, more than {MAX_TILES_PER_FRAME}")
+                tiles += [I.sample_geometry(w, h, width, height, ts=True, scale=s, patch_index=i) for i in range(1, n)]
+            except ValueError as e:
+                raise ValueError(f"frame {self.first + b}: {e}") from None
+            for g in tiles:
+                self.geoms.append(g)
+                self.frefs.append(I.frame_reference(g, off))
+                self.tile_frame.append(b)
+                table.append((b, int(round(g.boundary[0])) - g.hp, int(round(g.boundary[1])) - g.vp, 0))
+        self.NT = len(self.geoms)
+        self.tile_table = np.asarray(table, np.int32).reshape(self.NT, TILE_DESC)
+        self.desc = tiled_descriptors(self.sizes, self.offsets, self.scales)
+
+    def _tables(self, at):
+        self.tile_off = _align(at)
+        return self.tile_off + self.NT * TILE_DESC * 4
+
+    def _pack_tables(self, host):
+        host[self.tile_off:self.tile_off + self.tile_table.nbytes].view(np.int32)[:] = self.tile_table.reshape(-1)
 
 
 def _check_frame(f, i):
@@ -113,6 +193,13 @@ class FrameDetections:
         self.boxes, self.prob, self.rects, self.skipped, self.annotated = boxes, prob, rects, skipped, annotated
 
 
+class TiledFrameDetections(FrameDetections):
+    """FrameDetections of a tiled detector, and src int32 [n,2]: per box the tile it came from (its index among the tiles of the
+    batch, frames in order, a frame's tiles row-major over its grid) and its slot in that tile's detections."""
+
+    __slots__ = ("src",)
+
+
 class _Slot:
     def __init__(self):
         self.pin_in, self.pin_out, self.pin_total = None, None, None
@@ -127,7 +214,10 @@ def _pinned(t, need):
 class FrameDetector:
     """`FrameDetector(model).detect_frames(frames)`: see the module docstring.  conf_thres / nms_thres default to `model.get_threshs()`;
     at most `max_boxes` (<= top_k) boxes per frame are mapped and drawn, the most confident ones; `outline` is the one RGB triple of a
-    call (default `ImageColor.getrgb("red")`)."""
+    call (default `ImageColor.getrgb("red")`).  Subclasses override `_plan` (the batch's layout), `_batch_boxes` (the boxes of a batch) and
+    `_result_type`; everything else -- staging, drawing, the copy back, the one synchronisation -- is shared."""
+
+    _result_type = FrameDetections
 
     def __init__(self, model, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16):
         conf, nms, _ = model.get_threshs()
@@ -150,16 +240,28 @@ class FrameDetector:
         return next(self.model.parameters()).device
 
     # -- host half (worker thread): take a batch from the iterable, plan it, pack it into the slot's pinned buffer
+    def _plan(self, sizes, first):
+        return BatchPlan(sizes, self.width, self.height, self.top_k)
+
     def _stage(self, it, first, slot):
         frames = [_check_frame(f, first + i) for i, f in enumerate(islice(it, self.batch_size))]
         if not frames:
             return None
-        plan = BatchPlan([(f.shape[1], f.shape[0]) for f in frames], self.width, self.height, self.top_k)
+        plan = self._plan([(f.shape[1], f.shape[0]) for f in frames], first)
         slot.pin_in = _pinned(slot.pin_in, plan.in_bytes)
         plan.pack(slot.pin_in.numpy(), frames)
         return plan, slot
 
-    # -- device half: copy, resize, forward, post-process, draw, copy back, ONE synchronisation
+    # -- the boxes of a batch, enqueued on `st`: resize from the pool, eval forward, post-process -> device tensors boxes [B,K,4] fp32 in
+    #    the coordinates the plan's detect descriptors map from, prob [B,K], count [B] int32 (capped at max_boxes), src [B,K,2] or None
+    def _batch_boxes(self, plan, dbuf, host, pool, st):
+        imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
+        self.model.eval()
+        det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k)
+        count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
+        return det.boxes, det.prob, count, None
+
+    # -- device half: copy, boxes, draw, copy back, ONE synchronisation
     def _run(self, plan, slot, keep_on_device):
         L = _lib.lib()
         dev = self.device
@@ -170,16 +272,15 @@ class FrameDetector:
             dbuf[:plan.in_bytes].copy_(slot.pin_in[:plan.in_bytes], non_blocking=True)
             pool = dbuf[plan.pool_off:plan.pool_off + plan.pool_bytes]
             host = slot.pin_in.numpy()
-            imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
-            self.model.eval()
-            det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k)
-            count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
+            boxes, bprob, count, src = self._batch_boxes(plan, dbuf, host, pool, st)
             base = dbuf.data_ptr()
-            L.check(L.detect_draw_boxes(host.ctypes.data + plan.det_off, base + plan.det_off, B, det.boxes.data_ptr(), count.data_ptr(), K,
+            L.check(L.detect_draw_boxes(host.ctypes.data + plan.det_off, base + plan.det_off, B, boxes.data_ptr(), count.data_ptr(), K,
                                         base + plan.pool_off, plan.pool_bytes, *self.outline, base + plan.fb_off, base + plan.rect_off,
                                         base + plan.skip_off, st.cuda_stream), "detect_draw_boxes")
-            dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(det.prob.reshape(-1))
+            dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(bprob.reshape(-1))
             dbuf[plan.count_off:plan.count_off + B * 4].view(torch.int32).copy_(count)
+            if src is not None:
+                dbuf[plan.src_off:plan.src_off + B * K * 8].view(torch.int32).copy_(src.reshape(-1))
             lo = plan.fb_off if keep_on_device else plan.pool_off
             slot.pin_out = _pinned(slot.pin_out, plan.nbytes - lo)
             slot.pin_out[:plan.nbytes - lo].copy_(dbuf[lo:plan.nbytes], non_blocking=True)
@@ -203,7 +304,10 @@ class FrameDetector:
             else:
                 at = plan.pool_off - lo + off
                 ann = out[at:at + 3 * w * h].reshape(h, w, 3).copy()         # the pinned buffer is the next batch's
-            res.append(FrameDetections(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann))
+            r = self._result_type(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann)
+            if plan.src_off is not None:
+                r.src = table(plan.src_off, B * K * 8, np.int32, (B, K, 2))[b, :n].copy()
+            res.append(r)
         return res
 
     def detect_frames(self, frames, keep_on_device=False):
@@ -253,15 +357,27 @@ class ConeBatchPlan(BatchPlan):
 
     def __init__(self, sizes, width, height, K, max_cones):
         super().__init__(sizes, width, height, K)
-        self.per = min(int(max_cones), self.K)
-        self.cap = cap = self.B * self.per
-        self.total_off = self.nbytes
-        self.owner_off = self.total_off + 16
-        self.window_off = _align(self.owner_off + cap * 8)
-        self.pts_off = _align(self.window_off + cap * 16)
-        self.centers_off = _align(self.pts_off + cap * NUM_KPT * 8)
-        self.kskip_off = _align(self.centers_off + cap * NUM_KPT * 8)
-        self.nbytes = _align(self.kskip_off + self.B * 4)
+        _append_cone_tables(self, max_cones)
+
+
+def _append_cone_tables(plan, max_cones):
+    plan.per = min(int(max_cones), plan.K)
+    plan.cap = cap = plan.B * plan.per
+    plan.total_off = plan.nbytes
+    plan.owner_off = plan.total_off + 16
+    plan.window_off = _align(plan.owner_off + cap * 8)
+    plan.pts_off = _align(plan.window_off + cap * 16)
+    plan.centers_off = _align(plan.pts_off + cap * NUM_KPT * 8)
+    plan.kskip_off = _align(plan.centers_off + cap * NUM_KPT * 8)
+    plan.nbytes = _align(plan.kskip_off + plan.B * 4)
+
+
+class TiledConeBatchPlan(TiledBatchPlan):
+    """TiledBatchPlan with ConeBatchPlan's tables behind it"""
+
+    def __init__(self, sizes, width, height, K, scales, max_cones, first=0):
+        super().__init__(sizes, width, height, K, scales, first)
+        _append_cone_tables(self, max_cones)
 
 
 def scatter_cones(owner, pts, centers, b, n):
@@ -313,14 +429,10 @@ class FrameConeDetector(FrameDetector):
         self.colours = colour_table(colours)
         self._return_crops = False
 
-    def _stage(self, it, first, slot):
-        frames = [_check_frame(f, first + i) for i, f in enumerate(islice(it, self.batch_size))]
-        if not frames:
-            return None
-        plan = ConeBatchPlan([(f.shape[1], f.shape[0]) for f in frames], self.width, self.height, self.top_k, self.max_cones)
-        slot.pin_in = _pinned(slot.pin_in, plan.in_bytes)
-        plan.pack(slot.pin_in.numpy(), frames)
-        return plan, slot
+    _result_type = FrameCones
+
+    def _plan(self, sizes, first):
+        return ConeBatchPlan(sizes, self.width, self.height, self.top_k, self.max_cones)
 
     def _run(self, plan, slot, keep_on_device):
         L = _lib.lib()
@@ -332,13 +444,10 @@ class FrameConeDetector(FrameDetector):
             dbuf[:plan.in_bytes].copy_(slot.pin_in[:plan.in_bytes], non_blocking=True)
             pool = dbuf[plan.pool_off:plan.pool_off + plan.pool_bytes]
             host = slot.pin_in.numpy()
-            imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
-            self.model.eval()
-            det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k)
-            count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
+            boxes, bprob, count, src = self._batch_boxes(plan, dbuf, host, pool, st)
             base = dbuf.data_ptr()
             desc_h, desc_d = host.ctypes.data + plan.det_off, base + plan.det_off
-            L.check(L.detect_map_boxes(desc_h, desc_d, B, det.boxes.data_ptr(), count.data_ptr(), K, plan.pool_bytes, base + plan.fb_off,
+            L.check(L.detect_map_boxes(desc_h, desc_d, B, boxes.data_ptr(), count.data_ptr(), K, plan.pool_bytes, base + plan.fb_off,
                                        base + plan.rect_off, base + plan.skip_off, st.cuda_stream), "detect_map_boxes")
             crops = torch.empty(max(padded_rows(plan.cap, self.bucket), 1), 3, S, S, dtype=torch.float32, device=dev)
             L.check(L.crop_resize_frames_u8(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.rect_off, count.data_ptr(), K,
@@ -357,14 +466,16 @@ class FrameConeDetector(FrameDetector):
                 self.keypoint_net.eval()
                 _hm, pts = self.keypoint_net(crops[:rows])
                 dbuf[plan.pts_off:plan.pts_off + M * NUM_KPT * 8].view(torch.float32).copy_(pts[:M].reshape(-1))
-            L.check(L.detect_draw_boxes(desc_h, desc_d, B, det.boxes.data_ptr(), count.data_ptr(), K, base + plan.pool_off, plan.pool_bytes,
+            L.check(L.detect_draw_boxes(desc_h, desc_d, B, boxes.data_ptr(), count.data_ptr(), K, base + plan.pool_off, plan.pool_bytes,
                                         *self.outline, base + plan.fb_off, base + plan.rect_off, base + plan.skip_off, st.cuda_stream),
                     "detect_draw_boxes")
             L.check(L.kpt_draw_points(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.pts_off, base + plan.window_off,
                                       base + plan.owner_off, M, self.colours.ctypes.data, base + plan.centers_off, base + plan.kskip_off,
                                       st.cuda_stream), "kpt_draw_points")
-            dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(det.prob.reshape(-1))
+            dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(bprob.reshape(-1))
             dbuf[plan.count_off:plan.count_off + B * 4].view(torch.int32).copy_(count)
+            if src is not None:
+                dbuf[plan.src_off:plan.src_off + B * K * 8].view(torch.int32).copy_(src.reshape(-1))
             lo = plan.fb_off if keep_on_device else plan.pool_off
             slot.pin_out = _pinned(slot.pin_out, plan.nbytes - lo)
             slot.pin_out[:plan.nbytes - lo].copy_(dbuf[lo:plan.nbytes], non_blocking=True)
@@ -393,7 +504,9 @@ class FrameConeDetector(FrameDetector):
             else:
                 at = plan.pool_off - lo + off
                 ann = out[at:at + 3 * w * h].reshape(h, w, 3).copy()         # the pinned buffer is the next batch's
-            r = FrameCones(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann)
+            r = self._result_type(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann)
+            if plan.src_off is not None:
+                r.src = table(plan.src_off, B * K * 8, np.int32, (B, K, 2))[b, :n].copy()
             r.keypoints, r.keypoints_frame, r.has_crop, rows = scatter_cones(owner, kpts, centers, b, n)
             r.skipped_points = int(kskip[b])
             r.crops = crops_host[rows] if crops_host is not None else None
@@ -404,6 +517,92 @@ class FrameConeDetector(FrameDetector):
         """as FrameDetector.detect_frames -> yields one `FrameCones` per frame, in order"""
         self._return_crops = bool(return_crops)
         return super().detect_frames(frames, keep_on_device)
+
+
+# ------------------------------------------------------------------------------------------------- tile-and-scale inference (DESIGN.md §22)
+class TiledFrameCones(FrameCones):
+    """FrameCones of a tiled detector, and src int32 [n,2] as in TiledFrameDetections"""
+
+    __slots__ = ("src",)
+
+
+class _Tiled:
+    """The tiled front of a detector: the frame is scaled and cut into the tiles training sees (`ImageLabelBatches(ts=True)`), every tile
+    goes through the network at its native size, and mdcv_detect_merge_tiles (csrc/detect_tiles.hip) makes the tiles' detections one list
+    per frame.  Per batch, on the detector's one stream: all tiles resized from the pool in one launch, the eval forward and
+    `detect_postprocess` in chunks of `tile_batch` tiles, ONE merge launch -- no count is read by the host."""
+
+    def _init_tiles(self, scale, tile_batch, contain_thres):
+        if not callable(scale):
+            value = float(scale)
+            scale = lambda w, h: value                                       # noqa: E731
+        self.scale = scale
+        self.tile_batch = int(tile_batch)
+        if self.tile_batch < 1:
+            raise ValueError(f"{type(self).__name__}: tile_batch must be positive, got {tile_batch}")
+        self.contain_thres = -1.0 if contain_thres is None else float(contain_thres)      # negative: the seam rule is off
+        if contain_thres is not None and not self.contain_thres >= 0.0:
+            raise ValueError(f"{type(self).__name__}: contain_thres must be None or >= 0, got {contain_thres}")
+
+    def _scales(self, sizes):
+        return [float(self.scale(w, h)) for w, h in sizes]
+
+    def _batch_boxes(self, plan, dbuf, host, pool, st):
+        L = _lib.lib()
+        B, K, NT = plan.B, plan.K, plan.NT
+        imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)      # [NT,C,H,W]
+        self.model.eval()
+        dets = [detect_postprocess(self.model(imgs[at:at + self.tile_batch]), None, self.conf_thres, self.nms_thres, 0.5, self.width,
+                                   self.height, self.top_k) for at in range(0, NT, self.tile_batch)]
+        one = len(dets) == 1
+        tboxes = dets[0].boxes if one else torch.cat([d.boxes for d in dets])
+        tprob = dets[0].prob if one else torch.cat([d.prob for d in dets])
+        tcount = dets[0].count if one else torch.cat([d.count for d in dets])
+        dev = dbuf.device
+        boxes = torch.empty(B, K, 4, dtype=torch.float32, device=dev)        # the kernel writes every entry (zeros past count[b])
+        prob = torch.empty(B, K, dtype=torch.float32, device=dev)
+        src = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
+        count = torch.empty(B, dtype=torch.int32, device=dev)
+        L.check(L.detect_merge_tiles(tboxes.data_ptr(), tprob.data_ptr(), tcount.data_ptr(), host.ctypes.data + plan.tile_off,
+                                     dbuf.data_ptr() + plan.tile_off, NT, K, B, self.nms_thres, self.contain_thres, K, boxes.data_ptr(),
+                                     prob.data_ptr(), src.data_ptr(), count.data_ptr(), st.cuda_stream), "detect_merge_tiles")
+        if self.max_boxes < self.top_k:
+            count = count.clamp(max=self.max_boxes)
+        return boxes, prob, count, src
+
+
+class TiledFrameDetector(_Tiled, FrameDetector):
+    """`TiledFrameDetector(model, scale).detect_frames(frames)`: FrameDetector's interface on the tiles training sees (`ts=True`), so a
+    cone is detected at the pixel size the model learnt it at instead of shrunk with the whole frame.  `scale`: a float, or a callable
+    (frame_w, frame_h) -> float (the data set's scales are per camera size).  Boxes of overlapping tiles are merged by the greedy NMS at
+    `nms_thres`; `contain_thres` (None: off) also removes a box of one tile that lies to more than that fraction of the smaller area
+    inside a more confident box of another tile -- the part of a cone a tile edge cut off.  Yields `TiledFrameDetections` (boxes in
+    frame pixels: merged box / scale).  ONE host synchronisation per batch."""
+
+    _result_type = TiledFrameDetections
+
+    def __init__(self, model, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
+                 tile_batch=32, contain_thres=None):
+        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size)
+        self._init_tiles(scale, tile_batch, contain_thres)
+
+    def _plan(self, sizes, first):
+        return TiledBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), first)
+
+
+class TiledFrameConeDetector(_Tiled, FrameConeDetector):
+    """`TiledFrameConeDetector(model, keypoint_net, scale)`: TiledFrameDetector's boxes carried through FrameConeDetector's crop ->
+    key-point -> draw chain (the crops are cut from the untouched full-resolution frames in the pool).  Yields `TiledFrameCones`."""
+
+    _result_type = TiledFrameCones
+
+    def __init__(self, model, keypoint_net, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0),
+                 batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None):
+        super().__init__(model, keypoint_net, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, max_cones, bucket, colours)
+        self._init_tiles(scale, tile_batch, contain_thres)
+
+    def _plan(self, sizes, first):
+        return TiledConeBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), self.max_cones, first)
 
 
 # --------------------------------------------------------------------------------------------- the reference's two functions (detect.py)
@@ -422,40 +621,45 @@ def _save(annotated, path):
     return path
 
 
-def _detector(model, device, conf_thres, nms_thres, **kw):
+def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, contain_thres=None, **kw):
     """`device` is where the reference moves its input (detect.py:78) and where the caller has put the model (detect.py:51): the batches
-    are built on the model's device, so the two must be the same GPU.  None: the model's device."""
+    are built on the model's device, so the two must be the same GPU.  None: the model's device.  `tiles`: a TiledFrameDetector at
+    `scale` with `contain_thres`; otherwise those two are not looked at."""
     if device is not None:
         want, have = torch.device(device), next(model.parameters()).device
         if want.type != "cuda":
             raise _lib.MdcvError(f"detect: device {device!r} is not a GPU; there is no CPU fallback")
         if have.type != "cuda" or (want.index is not None and want.index != have.index):
             raise ValueError(f"detect: device {device!r} is not the model's device {str(have)!r}; move the model there first, as the reference's main does")
+    if tiles:
+        return TiledFrameDetector(model, scale, conf_thres=conf_thres, nms_thres=nms_thres, contain_thres=contain_thres, **kw)
     return FrameDetector(model, conf_thres=conf_thres, nms_thres=nms_thres, **kw)
 
 
-def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres):
+def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres, *, tiles=False, scale=1.0, contain_thres=None):
     """detect.py:60-111 for one RGB image file: mode 'image' saves under `output_path` with the file's own name, any other mode saves over
     `target_path` (the reference's rule for its dumped video frames); the saved path is returned.  With no detection the image is
     saved unannotated.  `device` must be the GPU the model is on (or None).  Each call builds its own detector: for many files use `detect`
-    on their directory."""
+    on their directory.  Keyword-only `tiles=True`: tile-and-scale inference at `scale` (TiledFrameDetector), the counterpart of training
+    with ts=True; the defaults are the reference's whole-frame pad and resize."""
     frame = _open_rgb(target_path)
-    res = next(iter(_detector(model, device, conf_thres, nms_thres, batch_size=1).detect_frames([frame])))
+    res = next(iter(_detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=1).detect_frames([frame])))
     if mode == "image":
         return _save(res.annotated, os.path.join(output_path, target_path.split("/")[-1]))
     return _save(res.annotated, target_path)
 
 
-def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16):
+def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16, *, tiles=False, scale=1.0, contain_thres=None):
     """detect.py:113-196.  An image file (.jpg / .jpeg / .png / .tif) goes through `single_img_detect`; a directory has its image files,
     sorted by name, detected in batches of `batch_size` and written to `output_path` under their own names (-> the list of paths).
-    Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead."""
+    Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead.
+    Keyword-only `tiles`, `scale`, `contain_thres`: as in `single_img_detect`."""
     ext = os.path.splitext(target_path)[-1].lower()
     if os.path.isdir(target_path):
         names = sorted(f for f in os.listdir(target_path)
                        if os.path.splitext(f)[-1].lower() in IMG_FORMATS and os.path.isfile(os.path.join(target_path, f)))
         print(f"Detection Mode is: directory ({len(names)} images)")
-        det = _detector(model, device, conf_thres, nms_thres, batch_size=batch_size)
+        det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=batch_size)
         frames = (_open_rgb(os.path.join(target_path, f)) for f in names)
         paths = [_save(res.annotated, os.path.join(output_path, f)) for f, res in zip(names, det.detect_frames(frames))]
         print(f"Please check output images at {output_path}")
@@ -468,6 +672,6 @@ def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch
         raise ValueError(f"{target_path}: not an image file ({', '.join(IMG_FORMATS)}) or a directory")
     print("Detection Mode is: image")
     path = single_img_detect(target_path=target_path, output_path=output_path, mode="image", model=model, device=device,
-                             conf_thres=conf_thres, nms_thres=nms_thres)
+                             conf_thres=conf_thres, nms_thres=nms_thres, tiles=tiles, scale=scale, contain_thres=contain_thres)
     print(f"Please check output image at {path}")
     return path
