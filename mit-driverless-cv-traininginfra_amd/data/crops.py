@@ -21,7 +21,6 @@ shared with `mdcv_crop_resize_u8` and `SyntheticConeCrops`.
 import hashlib
 import math
 import os
-from concurrent.futures import ThreadPoolExecutor
 from functools import lru_cache
 
 import numpy as np
@@ -29,16 +28,12 @@ import torch
 
 from .. import _lib
 from . import framecache
+from .staging import Layout, StagedBatches, align as _align, copy_fills_device, copy_fills_host, default_decode as _default_decode, fills_behind
 
 DESC = 20                                # MDCV_KPTLOAD_DESC
 MIN_SIZE, MAX_SIZE, MAX_SIDE = 16, 256, 4096          # MDCV_KPTLOAD_MIN_SIZE / MAX_SIZE / MAX_SIDE
 NUM_KPT = 7
 _F32 = np.float32
-
-
-def _default_decode(path):
-    from PIL import Image
-    return Image.open(path).convert("RGB")
 
 
 def _default_probe(path):
@@ -154,17 +149,9 @@ def zero_sum_maps(hot, h, w, size):
 
 
 # -------------------------------------------------------------------------------------------------------------------- the batch
-def _align(n, a=16):
-    return (n + a - 1) // a * a
-
-
-class _Packed:
-    pass
-
-
 def pack_layout(shapes):
     """Byte layout of one batch's staging buffer for crops of `shapes` [(h, w)]: [descriptors][points][pixels]"""
-    p = _Packed()
+    p = Layout()
     p.B = len(shapes)
     p.desc_off, p.pts_off = 0, _align(p.B * DESC * 4)
     p.pix_off = _align(p.pts_off + p.B * NUM_KPT * 2 * 4)
@@ -247,12 +234,7 @@ def transform_batch(crops, labels, size, device=None, names=None):
     return imgs, hm, pts
 
 
-class _Slot:
-    def __init__(self):
-        self.pinned, self.event = None, None
-
-
-class ConeCropBatches:
+class ConeCropBatches(StagedBatches):
     """Iterable of `(imgs [B,3,S,S], heatmaps [B,7,S,S], points [B,7,2], image_names, orig_sizes)`, the three tensors fp32 on the device:
     the batches that `DataLoader(ConeDataset(images, labels, dataset_path, target_image_size, ...), batch_size, shuffle=False)` yields.
     `image_names` is the list of `name.split(".")[0]`; `orig_sizes` is `[h, w, c]` as three int64 `[B]` tensors, what the default collate
@@ -260,9 +242,9 @@ class ConeCropBatches:
 
     `images`, `labels`: what `load_train_csv_dataset` returns (names relative to `dataset_path`; `[7,2]` (x, y) labels in the pixels of
     the original crop).  `target_image_size`: S or (S, S), 16 <= S <= 256.  `decode(path)` -> a PIL image or an (H, W, 3) uint8 RGB
-    array (default: `PIL.Image.open(path).convert('RGB')`), run on `num_workers` threads.  With `prefetch`, batch i+1 is decoded and
-    staged while batch i is consumed; its copy and launch run on a side stream that the consumer's stream waits for when the batch is
-    handed over.  `.incorrect_labels` collects the names whose labels give an all-NaN heat-map (module docstring).
+    array (default: `PIL.Image.open(path).convert('RGB')`), run on `num_workers` threads.  With `prefetch`, the next batches are decoded
+    and staged while one is consumed.  `.incorrect_labels` collects the names whose labels give an all-NaN heat-map (module
+    docstring).
 
     `cache_bytes`: None, or the HBM budget of a device-resident crop cache (mdcv/data/framecache.py): a crop is decoded
     once in the loader's lifetime and read from the pool afterwards; same outputs.  The label CSV has no sizes, so the constructor asks
@@ -285,14 +267,9 @@ class ConeCropBatches:
         self.dataset_path, self.size, self.batch_size = dataset_path, check_size(target_image_size), int(batch_size)
         if self.batch_size < 1:
             raise ValueError("ConeCropBatches: batch_size must be positive")
-        self.num_workers = int(num_workers) if num_workers is not None else max(1, min(16, os.cpu_count() or 1))
-        self.decode, self.prefetch = decode or _default_decode, bool(prefetch)
-        self._device = device
         self.dataset = range(len(self.images))
         self.incorrect_labels = []
-        self._pool = None
-        self._slots = [_Slot() for _ in range(3)]
-        self._cache, self._last_ready = None, None
+        cache = None
         if cache_bytes is not None:
             probe = probe or _default_probe
             paths = [os.path.join(dataset_path, n) for n in self.images]
@@ -304,12 +281,8 @@ class ConeCropBatches:
             # behind the slots: room for one batch's staged crops, so that one `src` covers both kinds (one launch per batch)
             per = [sum(3 * w * h for w, h in sizes[i:i + self.batch_size]) for i in range(0, len(sizes), self.batch_size)]
             tail = framecache._round(max(per, default=0) + 1)
-            self._cache = framecache.FrameCache(paths, sizes, cache_bytes, limit=(1 << 31) - 1 - tail, tail=tail)
-
-    def cache_stats(self):
-        """None without `cache_bytes`; else hits / fills (samples that read the pool without / after decoding their file), misses by
-        reason (samples staged the old way), bytes_reserved (by admission) and pool_bytes (allocated, the staging tail included)."""
-        return None if self._cache is None else self._cache.stats()
+            cache = framecache.FrameCache(paths, sizes, cache_bytes, limit=(1 << 31) - 1 - tail, tail=tail)
+        self._init_staging(num_workers, decode, prefetch, device, cache)
 
     def __len__(self):
         return (len(self.images) + self.batch_size - 1) // self.batch_size
@@ -332,10 +305,7 @@ class ConeCropBatches:
 
     def _stage(self, bi, slot):
         idx = range(bi * self.batch_size, min(len(self.images), (bi + 1) * self.batch_size))
-        if self._pool is not None:
-            got = list(self._pool.map(self._sample, idx))
-        else:
-            got = [self._sample(i) for i in idx]
+        got = self._map(self._sample, idx)
         for i, g in zip(idx, got):
             if g[3]:
                 print("Incorrect Data Label Detected! Please revise the image label below and becoming the one with data!")
@@ -344,7 +314,7 @@ class ConeCropBatches:
                     self.incorrect_labels.append(self.images[i])
         crops, ents = [g[0] for g in got], [g[5] for g in got]
         p = pack_layout([(0, 0) if c is None else c.shape[:2] for c in crops])
-        p.fills, need, pooled, base = [], p.nbytes, None, 0
+        fills, pooled, base = [], None, 0
         if self._cache is not None:
             c = self._cache
             base = c.bytes_reserved                              # the tail of the pool: this batch's staged crops
@@ -352,17 +322,11 @@ class ConeCropBatches:
                 raise ValueError(f"batch {bi}: {p.src_bytes} bytes of staged crops, the cache planned for {c.tail} (a file decodes larger "
                                  f"than `probe` said)")
             pooled = [None if e is None else (e.offset, e.size[1], e.size[0]) for e in ents]
-            for e in c.take_fills(ents):                         # first sight: the whole crops ride behind the batch, one copy each
-                p.fills.append((e, need))
-                need = _align(need + e.nbytes)
-        if slot.event is not None:
-            slot.event.synchronize()                             # the previous copy out of this buffer has completed
-        if slot.pinned is None or slot.pinned.numel() < need:
-            slot.pinned = torch.empty(_align(need, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        host = slot.pinned.numpy()
+            fills = c.take_fills(ents)
+        p.fills, need = fills_behind(p.nbytes, fills)            # first sight: the whole crops ride behind the batch, one copy each
+        host = slot.buffer(need).numpy()
         pack_batch(host, p, crops, [g[1] for g in got], [g[2] for g in got], pooled, base)
-        for e, at in p.fills:
-            host[at:at + e.nbytes] = e.frame.reshape(-1)
+        copy_fills_host(host, p.fills)
         names = [self.images[i].split(".")[0] for i in idx]
         sizes = [torch.tensor([hw[0] for hw in (g[4] for g in got)], dtype=torch.int64),
                  torch.tensor([hw[1] for hw in (g[4] for g in got)], dtype=torch.int64), torch.full((len(got),), 3, dtype=torch.int64)]
@@ -383,66 +347,12 @@ class ConeCropBatches:
                 dbuf.copy_(slot.pinned[:p.pix_off], non_blocking=True)
                 if p.src_bytes:
                     pool[tail:tail + p.src_bytes].copy_(slot.pinned[p.pix_off:p.pix_off + p.src_bytes], non_blocking=True)
-                for e, at in p.fills:
-                    pool[e.offset:e.offset + e.nbytes].copy_(slot.pinned[at:at + e.nbytes], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self._stream)
-            slot.event = ev
-            if self._cache is not None:
-                self._cache.filled([e for e, _ in p.fills], ev)
+                copy_fills_device(pool, slot.pinned, p.fills)
+            self._copied(slot, p.fills)
             imgs, hm = launch_batch(dbuf, slot.pinned.numpy(), p, self.size, self._stream, pool)
             pts = dbuf[p.pts_off:p.pts_off + p.B * NUM_KPT * 8].view(torch.float32).view(p.B, NUM_KPT, 2).clone()
-            ready = torch.cuda.Event()
-            ready.record(self._stream)
-            self._last_ready = ready
-        return imgs, hm, pts, names, sizes, ready
-
-    @property
-    def device(self):
-        if self._device is None:
-            return torch.device("cuda", torch.cuda.current_device())
-        return torch.device(self._device)
+            return imgs, hm, pts, names, sizes, self._ready()     # the next epoch waits for it: this launch reads the pool's tail
 
     def __iter__(self):
         _lib.require_gpu()
-        dev = self.device
-        self._stream = torch.cuda.Stream(dev)
-        if self._cache is not None:
-            self._cache.restart()
-            if self._cache.pool is None:
-                with torch.cuda.device(dev):
-                    self._cache.ensure_pool(dev)                 # allocated on the consumer's stream, written on the side streams
-                    self._stream.wait_stream(torch.cuda.current_stream(dev))
-            if self._last_ready is not None:                     # an earlier epoch's stream: its fills, and its last launch reading the tail
-                self._stream.wait_event(self._last_ready)
-        nb = len(self)
-        if self.num_workers > 1 and self._pool is None:
-            self._pool = ThreadPoolExecutor(self.num_workers, thread_name_prefix="mdcv-decode")
-        stager = ThreadPoolExecutor(1, thread_name_prefix="mdcv-stage") if self.prefetch else None
-        try:
-            pending = {}
-            for bi in range(nb):
-                if self.prefetch:
-                    for j in range(bi, min(nb, bi + 3)):
-                        if j not in pending:
-                            pending[j] = stager.submit(self._stage, j, self._slots[j % 3])
-                staged = pending.pop(bi).result() if self.prefetch else self._stage(bi, self._slots[bi % 3])
-                imgs, hm, pts, names, sizes, ready = self._enqueue(staged)
-                cons = torch.cuda.current_stream(dev)
-                cons.wait_event(ready)
-                for t in (imgs, hm, pts):
-                    t.record_stream(cons)
-                yield imgs, hm, pts, names, sizes
-        finally:
-            if stager is not None:
-                stager.shutdown(wait=True, cancel_futures=True)
-
-    def close(self):
-        if self._pool is not None:
-            self._pool.shutdown(wait=True)
-            self._pool = None
-        if self._cache is not None:
-            if self._cache.pool is not None and getattr(self, "_stream", None) is not None:
-                self._cache.pool.record_stream(self._stream)     # the last epoch's launch may still read it
-            self._cache.close()
-            self._last_ready = None
+        yield from self._batches(len(self), self._stage)

@@ -24,8 +24,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..yolo.detect import (DETECT_DESC, IMG_FORMATS, KPT_COLOURS_RGB, NUM_KPT, _align, _check_frame, _open_rgb, _pinned, colour_table,
-                           frame_offsets)
+from ..data.staging import align as _align, copy_back, pinned, upload
+from ..yolo.detect import DETECT_DESC, IMG_FORMATS, KPT_COLOURS_RGB, NUM_KPT, _check_frame, _open_rgb, _save, colour_table, frame_offsets
 
 MIN_SIZE, MAX_SIZE, MAX_SIDE = 16, 256, 4096          # MDCV_KPTLOAD_MIN_SIZE / MAX_SIZE / MAX_SIDE
 _ONE = int(np.array([1.0], np.float64).view(np.int64)[0])
@@ -103,13 +103,12 @@ class KeypointDetector:
         dev = self.device
         plan = CropBatchPlan([(c.shape[1], c.shape[0]) for c in crops], self.size)
         B, S = plan.B, plan.S
-        self._pin_in = _pinned(self._pin_in, plan.in_bytes)
+        self._pin_in = pinned(self._pin_in, plan.in_bytes)
         host = self._pin_in.numpy()
         plan.pack(host, crops)
         with torch.cuda.device(dev), torch.no_grad():
             st = torch.cuda.current_stream(dev)
-            dbuf = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
-            dbuf[:plan.in_bytes].copy_(self._pin_in[:plan.in_bytes], non_blocking=True)
+            dbuf = upload(self._pin_in, plan.in_bytes, plan.nbytes, dev)
             base = dbuf.data_ptr()
             desc_h, desc_d = host.ctypes.data + plan.desc_off, base + plan.desc_off
             imgs = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
@@ -126,23 +125,14 @@ class KeypointDetector:
                                       base + plan.owner_off, B, self.colours.ctypes.data, base + plan.centers_off, base + plan.skip_off,
                                       st.cuda_stream), "kpt_draw_points")
             L.check(L.kpt_heatmap_mosaic(hm.data_ptr(), B, S, base + plan.mosaic_off, st.cuda_stream), "kpt_heatmap_mosaic")
-            lo = plan.pool_off
-            self._pin_out = _pinned(self._pin_out, plan.nbytes - lo)
-            self._pin_out[:plan.nbytes - lo].copy_(dbuf[lo:plan.nbytes], non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(st)
-            done.synchronize()                                   # the batch's one host synchronisation
-        out = self._pin_out.numpy()
-        if int(out[plan.total_off - lo:plan.total_off - lo + 4].view(np.int32)[0]) != B:
+            self._pin_out, table = copy_back(dbuf, plan.pool_off, self._pin_out, st)      # the batch's one host synchronisation
+        if int(table(plan.total_off, 4, np.int32, (1,))[0]) != B:
             raise _lib.MdcvError("KeypointDetector: the resize kernel refused a crop the host had accepted")
-
-        def table(off, nbytes, dtype, shape):
-            return out[off - lo:off - lo + nbytes].view(dtype).reshape(shape).copy()          # the pinned buffer is the next batch's
-        kpts = table(plan.pts_off, B * NUM_KPT * 8, np.float32, (B, NUM_KPT, 2))
-        centers = table(plan.centers_off, B * NUM_KPT * 8, np.int32, (B, NUM_KPT, 2))
-        mosaic = table(plan.mosaic_off, B * NUM_KPT * S * S, np.uint8, (B, NUM_KPT * S, S))
+        kpts = table(plan.pts_off, B * NUM_KPT * 8, np.float32, (B, NUM_KPT, 2)).copy()       # the pinned buffer is the next batch's
+        centers = table(plan.centers_off, B * NUM_KPT * 8, np.int32, (B, NUM_KPT, 2)).copy()
+        mosaic = table(plan.mosaic_off, B * NUM_KPT * S * S, np.uint8, (B, NUM_KPT * S, S)).copy()
         for b, (off, (w, h)) in enumerate(zip(plan.offsets, plan.sizes)):
-            yield kpts[b], centers[b], table(plan.pool_off + off, 3 * w * h, np.uint8, (h, w, 3)), mosaic[b]
+            yield kpts[b], centers[b], table(plan.pool_off + off, 3 * w * h, np.uint8, (h, w, 3)).copy(), mosaic[b]
 
     def detect_crops(self, crops):
         """crops: any iterable of (H, W, 3) uint8 RGB arrays (sizes may differ) -> yields, per crop and in order, (keypoints float32 [7,2]
@@ -166,12 +156,6 @@ def load_model(model, img_size=80, device="cuda"):
     net = KeypointNet(NUM_KPT, (int(img_size), int(img_size)))
     net.load_state_dict(torch.load(model, map_location="cpu").get("model"))
     return net.to(device).eval()
-
-
-def _save(array, path):
-    from PIL import Image
-    Image.fromarray(array).save(path)
-    return path
 
 
 def detect(model, img, img_size=80, output="outputs/visualization/", flip=False, rotate=False, batch_size=16, ext=".jpg"):

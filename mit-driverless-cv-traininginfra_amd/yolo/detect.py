@@ -38,12 +38,13 @@ import torch
 
 from .. import _lib
 from ..data import images as I
+from ..data import staging
 from .postprocess import detect_postprocess, L_MAX_TOPK
 
 DETECT_DESC = 6                          # MDCV_DETECT_DESC
 IMG_FORMATS = (".jpg", ".jpeg", ".png", ".tif")         # detect.py:122-123
 VID_FORMATS = (".mov", ".avi", ".mp4")
-_align = I._align
+_align = staging.align
 
 
 # ------------------------------------------------------------------------------------------------------------- host layout (no GPU)
@@ -205,17 +206,11 @@ class _Slot:
         self.pin_in, self.pin_out, self.pin_total = None, None, None
 
 
-def _pinned(t, need):
-    if t is None or t.numel() < need:
-        t = torch.empty(_align(max(need, 1), 1 << 20), dtype=torch.uint8, pin_memory=True)
-    return t
-
-
 class FrameDetector:
     """`FrameDetector(model).detect_frames(frames)`: see the module docstring.  conf_thres / nms_thres default to `model.get_threshs()`;
     at most `max_boxes` (<= top_k) boxes per frame are mapped and drawn, the most confident ones; `outline` is the one RGB triple of a
     call (default `ImageColor.getrgb("red")`).  Subclasses override `_plan` (the batch's layout), `_batch_boxes` (the boxes of a batch) and
-    `_result_type`; everything else -- staging, drawing, the copy back, the one synchronisation -- is shared."""
+    `_result_type`; FrameConeDetector also `_annotate` and `_extras`; everything else -- staging, the copy back, the final synchronisation -- is shared."""
 
     _result_type = FrameDetections
 
@@ -248,7 +243,7 @@ class FrameDetector:
         if not frames:
             return None
         plan = self._plan([(f.shape[1], f.shape[0]) for f in frames], first)
-        slot.pin_in = _pinned(slot.pin_in, plan.in_bytes)
+        slot.pin_in = staging.pinned(slot.pin_in, plan.in_bytes)
         plan.pack(slot.pin_in.numpy(), frames)
         return plan, slot
 
@@ -261,36 +256,38 @@ class FrameDetector:
         count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
         return det.boxes, det.prob, count, None
 
+    def _draw_boxes(self, plan, dbuf, host, boxes, count, st):
+        L, base = _lib.lib(), dbuf.data_ptr()
+        L.check(L.detect_draw_boxes(host.ctypes.data + plan.det_off, base + plan.det_off, plan.B, boxes.data_ptr(), count.data_ptr(), plan.K,
+                                    base + plan.pool_off, plan.pool_bytes, *self.outline, base + plan.fb_off, base + plan.rect_off,
+                                    base + plan.skip_off, st.cuda_stream), "detect_draw_boxes")
+
+    # -- what is enqueued between the boxes and the copy back -> whatever `_extras` needs
+    def _annotate(self, plan, slot, dbuf, host, boxes, count, st):
+        self._draw_boxes(plan, dbuf, host, boxes, count, st)
+
+    # -- behind the final synchronisation -> add(r, b, n): what a subclass adds to frame b's result r with its n boxes
+    def _extras(self, plan, table, annotated):
+        return lambda r, b, n: None
+
     # -- device half: copy, boxes, draw, copy back, ONE synchronisation
     def _run(self, plan, slot, keep_on_device):
-        L = _lib.lib()
         dev = self.device
         B, K = plan.B, plan.K
         with torch.cuda.device(dev), torch.no_grad():
             st = torch.cuda.current_stream(dev)
-            dbuf = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
-            dbuf[:plan.in_bytes].copy_(slot.pin_in[:plan.in_bytes], non_blocking=True)
+            dbuf = staging.upload(slot.pin_in, plan.in_bytes, plan.nbytes, dev)
             pool = dbuf[plan.pool_off:plan.pool_off + plan.pool_bytes]
             host = slot.pin_in.numpy()
             boxes, bprob, count, src = self._batch_boxes(plan, dbuf, host, pool, st)
-            base = dbuf.data_ptr()
-            L.check(L.detect_draw_boxes(host.ctypes.data + plan.det_off, base + plan.det_off, B, boxes.data_ptr(), count.data_ptr(), K,
-                                        base + plan.pool_off, plan.pool_bytes, *self.outline, base + plan.fb_off, base + plan.rect_off,
-                                        base + plan.skip_off, st.cuda_stream), "detect_draw_boxes")
+            annotated = self._annotate(plan, slot, dbuf, host, boxes, count, st)
             dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(bprob.reshape(-1))
             dbuf[plan.count_off:plan.count_off + B * 4].view(torch.int32).copy_(count)
             if src is not None:
                 dbuf[plan.src_off:plan.src_off + B * K * 8].view(torch.int32).copy_(src.reshape(-1))
             lo = plan.fb_off if keep_on_device else plan.pool_off
-            slot.pin_out = _pinned(slot.pin_out, plan.nbytes - lo)
-            slot.pin_out[:plan.nbytes - lo].copy_(dbuf[lo:plan.nbytes], non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(st)
-            done.synchronize()                                   # the batch's one host synchronisation
-        out = slot.pin_out.numpy()
-
-        def table(off, nbytes, dtype, shape):
-            return out[off - lo:off - lo + nbytes].view(dtype).reshape(shape)
+            slot.pin_out, table = staging.copy_back(dbuf, lo, slot.pin_out, st)       # the batch's one (or last) host synchronisation
+            add = self._extras(plan, table, annotated)
         fb = table(plan.fb_off, B * K * 32, np.float64, (B, K, 4))
         rects = table(plan.rect_off, B * K * 16, np.int32, (B, K, 4))
         prob = table(plan.prob_off, B * K * 4, np.float32, (B, K))
@@ -302,11 +299,11 @@ class FrameDetector:
             if keep_on_device:
                 ann = pool[off:off + 3 * w * h].view(h, w, 3)
             else:
-                at = plan.pool_off - lo + off
-                ann = out[at:at + 3 * w * h].reshape(h, w, 3).copy()         # the pinned buffer is the next batch's
+                ann = table(plan.pool_off + off, 3 * w * h, np.uint8, (h, w, 3)).copy()      # the pinned buffer is the next batch's
             r = self._result_type(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann)
             if plan.src_off is not None:
                 r.src = table(plan.src_off, B * K * 8, np.int32, (B, K, 2))[b, :n].copy()
+            add(r, b, n)
             res.append(r)
         return res
 
@@ -434,84 +431,49 @@ class FrameConeDetector(FrameDetector):
     def _plan(self, sizes, first):
         return ConeBatchPlan(sizes, self.width, self.height, self.top_k, self.max_cones)
 
-    def _run(self, plan, slot, keep_on_device):
+    def _annotate(self, plan, slot, dbuf, host, boxes, count, st):
         L = _lib.lib()
-        dev = self.device
         B, K, S = plan.B, plan.K, self.size
-        with torch.cuda.device(dev), torch.no_grad():
-            st = torch.cuda.current_stream(dev)
-            dbuf = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
-            dbuf[:plan.in_bytes].copy_(slot.pin_in[:plan.in_bytes], non_blocking=True)
-            pool = dbuf[plan.pool_off:plan.pool_off + plan.pool_bytes]
-            host = slot.pin_in.numpy()
-            boxes, bprob, count, src = self._batch_boxes(plan, dbuf, host, pool, st)
-            base = dbuf.data_ptr()
-            desc_h, desc_d = host.ctypes.data + plan.det_off, base + plan.det_off
-            L.check(L.detect_map_boxes(desc_h, desc_d, B, boxes.data_ptr(), count.data_ptr(), K, plan.pool_bytes, base + plan.fb_off,
-                                       base + plan.rect_off, base + plan.skip_off, st.cuda_stream), "detect_map_boxes")
-            crops = torch.empty(max(padded_rows(plan.cap, self.bucket), 1), 3, S, S, dtype=torch.float32, device=dev)
-            L.check(L.crop_resize_frames_u8(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.rect_off, count.data_ptr(), K,
-                                            plan.per, S, crops.data_ptr(), base + plan.owner_off, base + plan.window_off,
-                                            base + plan.total_off, st.cuda_stream), "crop_resize_frames_u8")
-            if slot.pin_total is None:
-                slot.pin_total = torch.zeros(4, dtype=torch.int32, pin_memory=True)
-            slot.pin_total.copy_(dbuf[plan.total_off:plan.total_off + 16].view(torch.int32), non_blocking=True)
-            sized = torch.cuda.Event()
-            sized.record(st)
-            sized.synchronize()                                  # synchronisation 1 of 2: the crop total sizes the key-point batch
-            M = int(slot.pin_total.numpy()[0])
-            if M:
-                rows = padded_rows(M, self.bucket)
-                crops[M:rows].zero_()
-                self.keypoint_net.eval()
-                _hm, pts = self.keypoint_net(crops[:rows])
-                dbuf[plan.pts_off:plan.pts_off + M * NUM_KPT * 8].view(torch.float32).copy_(pts[:M].reshape(-1))
-            L.check(L.detect_draw_boxes(desc_h, desc_d, B, boxes.data_ptr(), count.data_ptr(), K, base + plan.pool_off, plan.pool_bytes,
-                                        *self.outline, base + plan.fb_off, base + plan.rect_off, base + plan.skip_off, st.cuda_stream),
-                    "detect_draw_boxes")
-            L.check(L.kpt_draw_points(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.pts_off, base + plan.window_off,
-                                      base + plan.owner_off, M, self.colours.ctypes.data, base + plan.centers_off, base + plan.kskip_off,
-                                      st.cuda_stream), "kpt_draw_points")
-            dbuf[plan.prob_off:plan.prob_off + B * K * 4].view(torch.float32).copy_(bprob.reshape(-1))
-            dbuf[plan.count_off:plan.count_off + B * 4].view(torch.int32).copy_(count)
-            if src is not None:
-                dbuf[plan.src_off:plan.src_off + B * K * 8].view(torch.int32).copy_(src.reshape(-1))
-            lo = plan.fb_off if keep_on_device else plan.pool_off
-            slot.pin_out = _pinned(slot.pin_out, plan.nbytes - lo)
-            slot.pin_out[:plan.nbytes - lo].copy_(dbuf[lo:plan.nbytes], non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(st)
-            done.synchronize()                                   # synchronisation 2 of 2
-            crops_host = crops[:M].cpu().numpy() if self._return_crops else None
-        out = slot.pin_out.numpy()
+        base = dbuf.data_ptr()
+        desc_h, desc_d = host.ctypes.data + plan.det_off, base + plan.det_off
+        L.check(L.detect_map_boxes(desc_h, desc_d, B, boxes.data_ptr(), count.data_ptr(), K, plan.pool_bytes, base + plan.fb_off,
+                                   base + plan.rect_off, base + plan.skip_off, st.cuda_stream), "detect_map_boxes")
+        crops = torch.empty(max(padded_rows(plan.cap, self.bucket), 1), 3, S, S, dtype=torch.float32, device=dbuf.device)
+        L.check(L.crop_resize_frames_u8(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.rect_off, count.data_ptr(), K,
+                                        plan.per, S, crops.data_ptr(), base + plan.owner_off, base + plan.window_off,
+                                        base + plan.total_off, st.cuda_stream), "crop_resize_frames_u8")
+        if slot.pin_total is None:
+            slot.pin_total = staging.pinned(None, 16, 16).view(torch.int32)
+        slot.pin_total.copy_(dbuf[plan.total_off:plan.total_off + 16].view(torch.int32), non_blocking=True)
+        sized = torch.cuda.Event()
+        sized.record(st)
+        sized.synchronize()                                      # synchronisation 1 of 2: the crop total sizes the key-point batch
+        M = int(slot.pin_total.numpy()[0])
+        if M:
+            rows = padded_rows(M, self.bucket)
+            crops[M:rows].zero_()
+            self.keypoint_net.eval()
+            _hm, pts = self.keypoint_net(crops[:rows])
+            dbuf[plan.pts_off:plan.pts_off + M * NUM_KPT * 8].view(torch.float32).copy_(pts[:M].reshape(-1))
+        self._draw_boxes(plan, dbuf, host, boxes, count, st)
+        L.check(L.kpt_draw_points(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.pts_off, base + plan.window_off,
+                                  base + plan.owner_off, M, self.colours.ctypes.data, base + plan.centers_off, base + plan.kskip_off,
+                                  st.cuda_stream), "kpt_draw_points")
+        return M, crops
 
-        def table(off, nbytes, dtype, shape):
-            return out[off - lo:off - lo + nbytes].view(dtype).reshape(shape)
-        fb = table(plan.fb_off, B * K * 32, np.float64, (B, K, 4))
-        rects = table(plan.rect_off, B * K * 16, np.int32, (B, K, 4))
-        prob = table(plan.prob_off, B * K * 4, np.float32, (B, K))
-        cnt = table(plan.count_off, B * 4, np.int32, (B,))
-        skipped = table(plan.skip_off, B * 4, np.int32, (B,))
+    def _extras(self, plan, table, annotated):
+        M, crops = annotated
+        crops_host = crops[:M].cpu().numpy() if self._return_crops else None
         owner = table(plan.owner_off, M * 8, np.int32, (M, 2))
         kpts = table(plan.pts_off, M * NUM_KPT * 8, np.float32, (M, NUM_KPT, 2))
         centers = table(plan.centers_off, M * NUM_KPT * 8, np.int32, (M, NUM_KPT, 2))
-        kskip = table(plan.kskip_off, B * 4, np.int32, (B,))
-        res = []
-        for b, (off, (w, h)) in enumerate(zip(plan.offsets, plan.sizes)):
-            n = min(int(cnt[b]), K)
-            if keep_on_device:
-                ann = pool[off:off + 3 * w * h].view(h, w, 3)
-            else:
-                at = plan.pool_off - lo + off
-                ann = out[at:at + 3 * w * h].reshape(h, w, 3).copy()         # the pinned buffer is the next batch's
-            r = self._result_type(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann)
-            if plan.src_off is not None:
-                r.src = table(plan.src_off, B * K * 8, np.int32, (B, K, 2))[b, :n].copy()
+        kskip = table(plan.kskip_off, plan.B * 4, np.int32, (plan.B,))
+
+        def add(r, b, n):
             r.keypoints, r.keypoints_frame, r.has_crop, rows = scatter_cones(owner, kpts, centers, b, n)
             r.skipped_points = int(kskip[b])
             r.crops = crops_host[rows] if crops_host is not None else None
-            res.append(r)
-        return res
+        return add
 
     def detect_frames(self, frames, keep_on_device=False, return_crops=False):
         """as FrameDetector.detect_frames -> yields one `FrameCones` per frame, in order"""

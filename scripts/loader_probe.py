@@ -214,7 +214,7 @@ def part_e(tmp, csv_path, steps=10):
         p = layout(*a, **k)
         staged.append(p.nbytes)
         return p
-    I.pack_layout = recording_layout
+    I.loader.pack_layout = recording_layout                  # where the loader looks it up
     try:
         syn = run(SyntheticCones(B, S, S, 16, 1, batches=steps + 4, seed=3))
         ld = I.ImageLabelBatches(csv_path, tmp, S, S, ts=True, lr_flip=False, batch_size=B, num_workers=16)
@@ -252,7 +252,7 @@ def part_e(tmp, csv_path, steps=10):
         print(f"    {ld.cache_stats()}")
         ld.close()
     finally:
-        I.pack_layout = layout
+        I.loader.pack_layout = layout
 
 
 def part_d(frames, repeats=5):
