@@ -597,6 +597,29 @@ int mdcv_comm_init(void** comm, int nranks, const void* id128, int rank);     /*
 int mdcv_comm_allreduce_sum(void* comm, float* buf, long long n, void* stream);   /* in place, enqueue-only */
 int mdcv_comm_destroy(void* comm);
 
+/* ---- anchor k-means of dataset preparation (CVC-YOLOv3/generate_kmeans_dataset_csvs.py:16-28 `assignment` / `update`, the loop of main at
+ *      139-149): batched Lloyd iterations over N boxes points[N][2] = (h, w) in fp64, K clusters, R independent restarts, bit-reproducible.
+ *      Limits: 1 <= K <= 16, 1 <= R <= 64, 1 <= N < 2^24; every coordinate finite, |x| < 2^14 and a multiple of 2^-64 (the CALLER checks the
+ *      coordinates: they are device data).  Arithmetic: assignment, for k in index order, q = fl(fl(dh*dh) + fl(dw*dw)), d = sqrt(q) correctly
+ *      rounded, the first minimum wins and a NaN centroid never wins; update c[k] = fl(S_k / n_k) per coordinate with S_k the EXACT sum of the
+ *      members rounded once to nearest-even (math.fsum), NaN for an empty cluster.  The sums are integers (fixed point, quantum 2^-64, integer
+ *      atomics): independent of the order blocks land in, so an unchanged assignment reproduces the same centroids and steps after a restart's
+ *      fixed point are no-ops.
+ *      Step 0 assigns to the initial centroids (the boxes init[R][K], indices into points); step t >= 1 updates from step t-1's assignment and
+ *      assigns again.  mdcv_kmeans_begin clears the workspace (ws: mdcv_kmeans_workspace_bytes, 8-byte aligned) and gathers the initial
+ *      centroids.  mdcv_kmeans_steps enqueues steps t0 .. t0+n_steps-1 (one launch each; the caller continues a run with t0 = the steps done so
+ *      far) and one small launch that writes record[R][MDCV_KMEANS_REC_HEAD + 2K], 8-byte words per restart: converged_at (the first step whose
+ *      assignment equals the previous step's, -1 = not yet), the low and high word of the distortion D = high * 2^32 + low =
+ *      sum_i floor(q_i * 2^32) of the last step, 1 if a centroid is NaN, then the centroids after the last step's update, [K][2] fp64 bits.
+ *      assign[R][N] holds the last step's assignment (state between calls). */
+#define MDCV_KMEANS_MAX_K 16
+#define MDCV_KMEANS_MAX_R 64
+#define MDCV_KMEANS_REC_HEAD 4
+long long mdcv_kmeans_workspace_bytes(long long N, int K, int R);     /* MDCV_EARG outside the limits */
+int mdcv_kmeans_begin(void* ws, const double* points, const int* init, long long N, int K, int R, void* stream);
+int mdcv_kmeans_steps(void* ws, const double* points, unsigned char* assign, long long* record, long long N, int K, int R, int t0,
+                      int n_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
