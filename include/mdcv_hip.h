@@ -620,6 +620,49 @@ int mdcv_kmeans_begin(void* ws, const double* points, const int* init, long long
 int mdcv_kmeans_steps(void* ws, const double* points, unsigned char* assign, long long* record, long long N, int K, int R, int t0,
                       int n_steps, void* stream);
 
+/* ---- dataset-level detection evaluation: COCO-style average precision over a whole validation set, csrc/detmap.hip.
+ *      The caller owns the dataset buffers, sized for `cap` images of K rows: score f32 [cap,K], cls i32 [cap,K], count i32 [cap],
+ *      status u32 [S,cap,K] (two bits per IoU threshold j at bit 2j: MDCV_DETMAP_FP / _TP / _IGNORED) and n_gt i64 [S,C], which the caller
+ *      zeroes before the first image.  Both calls are enqueue-only; every argument is checked before a device is touched (MDCV_EARG).
+ *      Limits: 1 <= K <= MDCV_NMS_MAX_TOPK, 0 <= T <= MDCV_DETMAP_MAX_GT, 1 <= J <= MDCV_DETMAP_MAX_THR thresholds in (0, 1],
+ *      1 <= S <= MDCV_DETMAP_MAX_RANGES ranges [lo, hi) of box area in px^2 with lo <= hi, 1 <= C <= MDCV_DETMAP_MAX_CLASSES,
+ *      cap * K <= MDCV_DETMAP_MAX_SLOTS, 0 <= first and first + B <= cap, B <= 65535.
+ *      mdcv_detmap_match: images first .. first+B-1 of the dataset.  Detections boxes [B,K,4] corner fp32, prob [B,K], cls [B,K] (NULL: class
+ *      0), count [B] (clamped to 0..K), rows most confident first (they are not sorted again).  Ground truth, gt_mode MDCV_DETMAP_GT_PIXELS:
+ *      gt [B,T,4] corner pixels, gt_cls [B,T] (NULL: 0), gt_ignore u8 [B,T] (NULL: none), gt_count [B]; MDCV_DETMAP_GT_LABELS: gt [B,T,5] the
+ *      loader's zero-padded (class, cx, cy, w, h) rows, converted with width / height by the fp32 operations of mdcv_detect_post (a row with
+ *      any of cx, cy, w, h <= 0 is padding), gt_cls / gt_ignore / gt_count not read.  iou_thr [J] and ranges [S][2] are HOST arrays.  A class
+ *      outside 0..C-1 (detection or ground truth) takes no part.  Per image, class, threshold and range the rule is COCOeval.evaluateImg: a
+ *      ground truth is ignored when flagged or when its area is outside the range; each detection, in row order, takes the unmatched
+ *      non-ignored ground truth of its class with the largest IoU >= thr (equal IoU: the higher index), else an unmatched ignored one by the
+ *      same rule; TP / IGNORED accordingly, unmatched: IGNORED when its own area is outside the range, else FP.  IoU and areas: the fp32
+ *      arithmetic of the NMS (nms.py:24, 44-59) with the detection as the kept box.
+ *      mdcv_detmap_finalize: over images 0 .. n_images-1.  A stable sort by (class, descending score) -- equal scores stay in image, then row
+ *      order -- then per (c, j, s): q [C,J,S,101,2] i64 = the precision envelope at recall levels k / 100 as (numerator, denominator) in
+ *      lowest terms, (0, 1) for a level never reached; tot [C,J,S,3] i64 = (n_gt, true positives, non-ignored detections); ap [C,J,S] f64 =
+ *      (sum over k = 0..100 in that order of (double)num / (double)den) / 101, or -1 where n_gt == 0.  err: one i32, bit 0 set when a valid
+ *      row's score is NaN or not positive (such a row is left out).  workspace: mdcv_detmap_finalize_workspace_bytes(cap, K) bytes, 8-byte
+ *      aligned (MDCV_EARG outside the limits, -2 when the sort's size query fails). */
+#define MDCV_DETMAP_MAX_GT 2048
+#define MDCV_DETMAP_MAX_THR 10
+#define MDCV_DETMAP_MAX_RANGES 4
+#define MDCV_DETMAP_MAX_CLASSES 1024
+#define MDCV_DETMAP_MAX_SLOTS 1073741824
+#define MDCV_DETMAP_CHUNK 1024
+#define MDCV_DETMAP_GT_PIXELS 0
+#define MDCV_DETMAP_GT_LABELS 1
+#define MDCV_DETMAP_FP 0
+#define MDCV_DETMAP_TP 1
+#define MDCV_DETMAP_IGNORED 2
+int mdcv_detmap_match(const float* boxes, const float* prob, const int* cls, const int* count, int B, int K, int gt_mode, const float* gt,
+                      const int* gt_cls, const unsigned char* gt_ignore, const int* gt_count, int T, float width, float height,
+                      const float* iou_thr, int J, const float* ranges, int S, int C, long long first, long long cap, float* ds_score,
+                      int* ds_cls, int* ds_count, unsigned* ds_status, long long* ds_n_gt, void* stream);
+long long mdcv_detmap_finalize_workspace_bytes(long long cap, int K);
+int mdcv_detmap_finalize(const float* ds_score, const int* ds_cls, const int* ds_count, const unsigned* ds_status, const long long* ds_n_gt,
+                         long long n_images, long long cap, int K, int J, int S, int C, long long* q, long long* tot, double* ap, int* err,
+                         void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
