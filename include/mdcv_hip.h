@@ -502,6 +502,51 @@ int mdcv_adam_step(float* params, const float* grads, float* exp_avg, float* exp
 int mdcv_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, int step, float lr, float momentum, float weight_decay,
                   float grad_scale, void* stream);
 
+/* ---- gradient guard (csrc/grad_guard.hip): global-norm clipping and dropping a step whose gradient is not finite, decided
+ *      on the device.  Four enqueue-only entry points on the caller's stream; no process state; nothing here waits for the GPU.
+ *
+ *      mdcv_grad_sumsq: partials[c] = the sum of (double)g[i] * (double)g[i] over chunk c = elements [c * CHUNK, min(n, (c + 1) * CHUNK)),
+ *      CHUNK = MDCV_GRAD_GUARD_CHUNK, for c < ceil(n / CHUNK).  Order inside a chunk: thread t of 256 adds
+ *      elements (r * 256 + t) * 4 + e for r = 0..3, e = 0..3 (elements beyond n add +0.0); the 256 sums are joined by the xor butterfly
+ *      of each wave (offsets 32, 16, .. 1) and then ((w0 + w1) + w2) + w3.  The order is a function of n alone: the grid (capped at
+ *      MDCV_GRAD_GUARD_MAX_GRID workgroups, which stride over the chunks) and the order in which workgroups run do not enter, and no
+ *      atomics are used.  grads 16-byte aligned, n >= 1; partials is caller-owned scratch, every word of it is written.
+ *
+ *      mdcv_grad_guard_finalize: one workgroup.  Thread t adds partials t, t + 256, .. in order, the 256 sums are joined as above, and
+ *      the block is written (ordinary stores):
+ *        sumsq                  the sum; finite exactly when every gradient is
+ *        norm                   (float)(fabs((double)grad_scale) * sqrt(sumsq))
+ *        coef                   max_norm > 0: fminf(1, max_norm / (norm + 1e-6f)) -- torch.nn.utils.clip_grad_norm_; otherwise 1
+ *        scale                  grad_scale * coef: what the guarded updates multiply every gradient by
+ *        finite, apply          apply = finite || !skip_nonfinite
+ *        attempted, applied, skipped, clipped   counters; clipped counts applied steps with a finite norm and coef < 1
+ *        max_norm_seen          the largest finite norm so far
+ *        bc1, bc2_sqrt          (float)(1 - beta1^t), (float)sqrt(1 - beta2^t) in double with t = applied + 1 (the count BEFORE this
+ *                               call): a skipped step leaves no trace in the bias correction.  beta^t is square-and-multiply from the
+ *                               low bit of t up (r = r * x on a set bit, then x = x * x while bits remain).  SGD passes 0 for both.
+ *      and history[attempted % ring] = norm (attempted BEFORE this call; ring == 0: no history).  The caller zeroes the block once.
+ *
+ *      mdcv_adam_step_guarded / mdcv_sgd_step_guarded: mdcv_adam_step / mdcv_sgd_step with grad_scale = block->scale, the bias
+ *      corrections from the block and "first step" = block->applied == 1 (this step is the first one applied); block->apply == 0: every
+ *      thread returns before it reads or writes params, grads or state.  Any 16-byte aligned slice may be passed, as to mdcv_adam_step.
+ *      These round every operation on its own (no fma contraction), so they differ from the unguarded kernels in the last bit. */
+#define MDCV_GRAD_GUARD_CHUNK 4096
+#define MDCV_GRAD_GUARD_MAX_GRID 2048
+typedef struct mdcv_grad_guard_block {
+  double sumsq;                                   /* byte  0 */
+  float norm, coef, scale, bc1, bc2_sqrt;         /* bytes 8, 12, 16, 20, 24 */
+  float max_norm_seen;                            /* byte 28 */
+  int finite, apply;                              /* bytes 32, 36 */
+  long long attempted, applied, skipped, clipped; /* bytes 40, 48, 56, 64; 72 bytes in all */
+} mdcv_grad_guard_block;
+int mdcv_grad_sumsq(const float* grads, long long n, double* partials, void* stream);
+int mdcv_grad_guard_finalize(const double* partials, long long n_partials, float grad_scale, float max_norm, int skip_nonfinite, double beta1,
+                             double beta2, mdcv_grad_guard_block* block, float* history, int ring, void* stream);
+int mdcv_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, const mdcv_grad_guard_block* block,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
+int mdcv_sgd_step_guarded(float* params, const float* grads, float* momentum_buf, long long n, const mdcv_grad_guard_block* block, float lr,
+                          float momentum, float weight_decay, void* stream);
+
 /* ---- per-step bookkeeping of the training loops in one launch (csrc/train_log.hip; CVC-YOLOv3/train.py:54,63-64,74-90 ;
  *      RektNet/train_eval.py:74-78): what the loops read back with `.item()` every step stays on the device.
  *      losses: n_losses addresses ON THE HOST (copied into the launch), each a device pointer to ONE fp32 or NULL (= 0.0f: RektNet's

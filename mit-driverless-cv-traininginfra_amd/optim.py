@@ -4,10 +4,168 @@
 launch over the model's flat fp32 parameter buffer (engine side: FlatParamsMixin), instead of the 222 / 54 per-tensor
 updates torch.optim performs for the reference (CVC-YOLOv3/train.py:180-187,72 ; RektNet/train_eval.py:263,72).
 Update rules, defaults and `param_groups[0]["lr"]` handling (LR schedulers) follow torch.optim.Adam / SGD.
+
+`guard=GradGuard(max_norm=..., skip_nonfinite=...)` puts two launches in front of the update (csrc/grad_guard.hip): the global
+gradient norm, the clip coefficient and the decision to drop a step whose gradient is not finite are formed on the device, and the update
+reads them from there.  Nothing waits for the GPU; `guard.stats()` reads the counters when somebody wants them.
 """
+import ctypes
+import math
+
 import torch
 
 from . import _lib
+
+GUARD_CHUNK = 4096          # include/mdcv_hip.h MDCV_GRAD_GUARD_CHUNK: elements per partial sum
+_BLOCK_WORDS = 9            # mdcv_grad_guard_block: 72 bytes
+
+
+class GradGuard:
+    """Device-side global-norm clipping and non-finite-step skipping for FusedAdam / FusedSGD (pass it as `guard=`).
+
+    max_norm        clip the global L2 norm of the (scaled) gradient to this, torch.nn.utils.clip_grad_norm_'s rule; None / 0: no clipping
+    skip_nonfinite  a step whose gradient holds a NaN or an Inf changes nothing: not a parameter, not a moment, not the bias correction
+    ring            how many of the latest norms `stats()` can return
+
+    Owns the control block (mdcv_grad_guard_block), the ring of norms behind it in the same allocation (so `stats()` is ONE host read) and
+    the partial-sum scratch, sized from the flat gradient buffer at first use.  One guard serves one optimizer.
+
+    Known limit: the guard acts between the backward and the update.  A step whose FORWARD already produced non-finite activations has
+    written them into the BatchNorm running statistics before the guard sees anything."""
+
+    def __init__(self, max_norm=None, skip_nonfinite=True, ring=1024):
+        if max_norm is not None and not (max_norm >= 0 and math.isfinite(max_norm)):
+            raise ValueError("GradGuard: max_norm must be None or a finite number >= 0 (0 = no clipping)")
+        if int(ring) < 1:
+            raise ValueError("GradGuard: ring must be >= 1")
+        self.max_norm = float(max_norm) if max_norm else 0.0
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.ring = int(ring)
+        self._buf = None            # int64 words: the block, then the ring of fp32 norms
+        self._partials = None
+        self._pending = None        # counters of a checkpoint loaded before the first step
+        self._seen = dict(attempted=0, applied=0, skipped=0, clipped=0)      # counters at the last summary()
+
+    def _ensure(self, device, n):
+        if self._buf is None or self._buf.device != device:
+            old = self._buf
+            self._buf = torch.zeros(_BLOCK_WORDS + (self.ring + 1) // 2, dtype=torch.int64, device=device)
+            if old is not None:
+                self._buf.copy_(old)
+            if self._pending is not None:
+                self._write_counters(self._pending)
+                self._pending = None
+        need = (n + GUARD_CHUNK - 1) // GUARD_CHUNK
+        if self._partials is None or self._partials.numel() < need or self._partials.device != device:
+            self._partials = torch.empty(need, dtype=torch.float64, device=device)
+
+    @property
+    def block_ptr(self):
+        return self._buf.data_ptr()
+
+    @property
+    def norm(self):
+        """the last measured norm: a device fp32 scalar view of the control block (a StepLog source, say); valid after the first step"""
+        if self._buf is None:
+            raise RuntimeError("GradGuard.norm: nothing has been measured yet")
+        return self._buf[1:2].view(torch.float32)[0]
+
+    def measure(self, gflat, grad_scale=1.0, betas=(0.0, 0.0)):
+        """enqueue sumsq -> finalize over `gflat` on the current stream (what a guarded step() does in front of its update)"""
+        _lib.require_gpu(gflat)
+        L = _lib.lib()
+        n = gflat.numel()
+        self._ensure(gflat.device, n)
+        s = torch.cuda.current_stream().cuda_stream
+        L.check(L.grad_sumsq(gflat.data_ptr(), n, self._partials.data_ptr(), s), "grad_sumsq")
+        # the betas as the update kernels see them: rounded to fp32, then widened
+        b1, b2 = (ctypes.c_float(b).value for b in betas)
+        L.check(L.grad_guard_finalize(self._partials.data_ptr(), (n + GUARD_CHUNK - 1) // GUARD_CHUNK, float(grad_scale), self.max_norm,
+                                      int(self.skip_nonfinite), b1, b2, self._buf.data_ptr(), self._buf[_BLOCK_WORDS:].data_ptr(), self.ring, s),
+                "grad_guard_finalize")
+
+    @staticmethod
+    def _parse(words):
+        """the block's fields from its 9 int64 words on the host"""
+        f = words[:_BLOCK_WORDS].view(torch.float32)
+        i = words[:_BLOCK_WORDS].view(torch.int32)
+        return dict(sumsq=float(words[:1].view(torch.float64)[0]), norm=float(f[2]), coef=float(f[3]), scale=float(f[4]), bc1=float(f[5]),
+                    bc2_sqrt=float(f[6]), max_norm=float(f[7]), finite=int(i[8]), apply=int(i[9]), attempted=int(words[5]),
+                    applied=int(words[6]), skipped=int(words[7]), clipped=int(words[8]))
+
+    def stats(self):
+        """ONE host read (it waits for the work queued so far): the block's fields (`norm` the last one, `max_norm` the largest finite one)
+        and `norms`, the ring's norms in step order -- the latest min(attempted, ring) of them; a non-finite step's norm is nan or inf"""
+        if self._buf is None:
+            d = dict(sumsq=0.0, norm=0.0, coef=1.0, scale=1.0, bc1=0.0, bc2_sqrt=0.0, max_norm=0.0, finite=1, apply=1, attempted=0, applied=0,
+                     skipped=0, clipped=0, norms=[])
+            d.update(self._pending or {})
+            return d
+        host = self._buf.cpu()
+        d = self._parse(host)
+        hist = host[_BLOCK_WORDS:].view(torch.float32)[:self.ring]
+        a = d["attempted"]
+        k = min(a, self.ring)
+        d["norms"] = [float(hist[j % self.ring]) for j in range(a - k, a)]
+        return d
+
+    def summary(self):
+        """`stats()` plus what happened since the last summary(): `steps`, `epoch_clipped`, `epoch_skipped`, and the `epoch_max` / `epoch_mean`
+        of the finite norms among those steps that are still in the ring (the training loops' one line per epoch)"""
+        d = self.stats()
+        steps = d["attempted"] - self._seen["attempted"]
+        d["steps"] = steps
+        d["epoch_clipped"] = d["clipped"] - self._seen["clipped"]
+        d["epoch_skipped"] = d["skipped"] - self._seen["skipped"]
+        fin = [x for x in d["norms"][max(0, len(d["norms"]) - steps):] if math.isfinite(x)] if steps > 0 else []
+        d["epoch_max"] = max(fin) if fin else float("nan")
+        d["epoch_mean"] = sum(fin) / len(fin) if fin else float("nan")
+        self._seen = {k: d[k] for k in self._seen}
+        return d
+
+    def summary_line(self, label_prefix, epoch):
+        d = self.summary()
+        return (f"{label_prefix} Epoch: {epoch}, grad norm max {d['epoch_max']:.4g} mean {d['epoch_mean']:.4g}, clipped {d['epoch_clipped']}, "
+                f"skipped {d['epoch_skipped']} of {d['steps']} steps")
+
+    def _write_counters(self, c):
+        w = torch.tensor([int(c.get(k, 0)) for k in ("attempted", "applied", "skipped", "clipped")], dtype=torch.int64)
+        self._buf[5:9].copy_(w)
+        self._buf[3:4].view(torch.float32)[1:2].copy_(torch.tensor([float(c.get("max_norm", 0.0))], dtype=torch.float32))
+        self._seen = {k: int(c.get(k, 0)) for k in self._seen}
+
+    def state_dict(self):
+        """the counters and the largest norm (one host read): a resumed run bias-corrects with the APPLIED count"""
+        d = self.stats()
+        return {k: d[k] for k in ("attempted", "applied", "skipped", "clipped", "max_norm")}
+
+    def load_state_dict(self, sd):
+        if self._buf is None:
+            self._pending = dict(sd)
+            self._seen = {k: int(sd.get(k, 0)) for k in self._seen}
+        else:
+            self._write_counters(sd)
+
+
+def grad_norm(model, grad_scale=1.0):
+    """The global L2 norm of the model's gradient times |grad_scale|: a device fp32 scalar, through the guard's two launches (the sum of
+    squares in fp64, in a fixed order) on the current stream.  No host wait."""
+    _lib.require_gpu()
+    _, gflat = model.flat_parameters()
+    _fold_grads(model)
+    g = GradGuard(ring=1)
+    g.measure(gflat, grad_scale)
+    return g.norm
+
+
+def _fold_grads(model):
+    """gradients normally ARE views of the flat gradient buffer (written in place by the backward plan); fold in anything that is not"""
+    for p in model._plist:
+        v = model._grad_view(p)
+        if p.grad is None:
+            v.zero_()
+        elif p.grad.data_ptr() != v.data_ptr():
+            v.copy_(p.grad)
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -18,6 +176,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         super().__init__(list(model.parameters()), defaults)
         self._step = 0
         self._state_bufs = None
+        self.guard = None
 
     def _flat(self, nstate):
         pflat, gflat = self.model.flat_parameters()
@@ -30,18 +189,15 @@ class _FlatOptimizer(torch.optim.Optimizer):
                              f"parameter buffer has {pflat.numel()} ({nstate} expected): the state belongs to another parameter layout")
         elif self._state_bufs[0].device != pflat.device:
             self._state_bufs = [b.to(pflat.device) for b in self._state_bufs]
-        # gradients normally ARE views of gflat (written in place by the backward plan); fold in anything that is not
-        for p in self.model._plist:
-            v = self.model._grad_view(p)
-            if p.grad is None:
-                v.zero_()
-            elif p.grad.data_ptr() != v.data_ptr():
-                v.copy_(p.grad)
+        _fold_grads(self.model)
         return pflat, gflat
 
     def state_dict(self):
-        return {"step": self._step, "state": [b.clone() for b in (self._state_bufs or [])], "param_groups": [
+        sd = {"step": self._step, "state": [b.clone() for b in (self._state_bufs or [])], "param_groups": [
             {k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        if self.guard is not None:
+            sd["guard"] = self.guard.state_dict()            # (one host read, at checkpoint time)
+        return sd
 
     def load_state_dict(self, sd):
         if sd["state"]:
@@ -54,6 +210,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._step = sd["step"]
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
+        if self.guard is not None:
+            # a checkpoint written without a guard: every one of its steps was applied
+            self.guard.load_state_dict(sd.get("guard") or dict(attempted=sd["step"], applied=sd["step"]))
 
 
 class FusedAdam(_FlatOptimizer):
@@ -64,9 +223,10 @@ class FusedAdam(_FlatOptimizer):
     operations per element; only the stream differs.  Readers of the parameters go through `model.flat_parameters()` /
     `synchronize()`, which order the current stream behind the update."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, pipeline=False):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, pipeline=False, guard=None):
         super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.pipeline = pipeline
+        self.guard = guard
         self._pstream = None
 
     def synchronize(self):
@@ -91,6 +251,14 @@ class FusedAdam(_FlatOptimizer):
         pp, gp, mp, vp = pflat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr()
         tab = plan.pack_table.data_ptr()
         hyp = (self._step, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(grad_scale))
+        # Guarded: every group reads ONE control block, written by the finalize that step() put on `cur` in front of the wait_stream above.
+        # The late groups run from the next forward, and the block must still be this step's when they do.  It is: the next finalize is
+        # enqueued by the next step(), whose `_flat()` -> `flat_parameters()` -> `_param_sync()` first launches every group still pending
+        # and makes `cur` wait for every group's event -- and in the training loop already the next forward has waited for every group
+        # in front of the backward that the next step() follows.  So no double buffering.  A skipped group's pack_weights_batched re-packs
+        # unchanged weights into the operands the forward reads: the same bytes as before, a little wasted bandwidth on a rare step.
+        blk = None if self.guard is None else self.guard.block_ptr
+        ghyp = hyp[1:6]
 
         def make(k, lo, hi, first, nl):
             def launch(after_stream):
@@ -100,7 +268,10 @@ class FusedAdam(_FlatOptimizer):
                     ps.wait_event(gate)
                 with torch.cuda.stream(ps):
                     s = ps.cuda_stream
-                    L.check(L.adam_step(pp + 4 * lo, gp + 4 * lo, mp + 4 * lo, vp + 4 * lo, hi - lo, *hyp, s), "adam_step")
+                    if blk is None:
+                        L.check(L.adam_step(pp + 4 * lo, gp + 4 * lo, mp + 4 * lo, vp + 4 * lo, hi - lo, *hyp, s), "adam_step")
+                    else:
+                        L.check(L.adam_step_guarded(pp + 4 * lo, gp + 4 * lo, mp + 4 * lo, vp + 4 * lo, hi - lo, blk, *ghyp, s), "adam_step_guarded")
                     L.check(L.pack_weights_batched(plan.dtype, tab + 72 * first, nl, plan.pack_eq_taps, s), "pack_weights_batched")
                     ev = torch.cuda.Event()
                     ev.record(ps)
@@ -126,20 +297,28 @@ class FusedAdam(_FlatOptimizer):
         pflat, gflat = self._flat(2)
         m, v = self._state_bufs
         self._step += 1
+        if self.guard is not None:
+            self.guard.measure(gflat, grad_scale, g["betas"])                # sumsq -> finalize on the current stream; the update reads the block
         plan = getattr(self.model, "_last_train_plan", None)
         if self.pipeline and plan is not None and not plan.use_graph and pflat.is_cuda and getattr(plan, "pack_table", None) is not None:
             groups = plan.ensure_param_groups(pflat)
             if groups:
                 self._pipelined(L, plan, groups, pflat, gflat, m, v, g, grad_scale)
                 return
+        if self.guard is not None:
+            L.check(L.adam_step_guarded(pflat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), pflat.numel(), self.guard.block_ptr,
+                                        float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                                        torch.cuda.current_stream().cuda_stream), "adam_step_guarded")
+            return
         L.check(L.adam_step(pflat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), pflat.numel(), self._step, float(g["lr"]),
                             float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(grad_scale),
                             torch.cuda.current_stream().cuda_stream), "adam_step")
 
 
 class FusedSGD(_FlatOptimizer):
-    def __init__(self, model, lr=1e-3, momentum=0.0, weight_decay=0.0):
+    def __init__(self, model, lr=1e-3, momentum=0.0, weight_decay=0.0, guard=None):
         super().__init__(model, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        self.guard = guard
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
@@ -148,5 +327,11 @@ class FusedSGD(_FlatOptimizer):
         g = self.param_groups[0]
         pflat, gflat = self._flat(1)
         self._step += 1
+        if self.guard is not None:
+            self.guard.measure(gflat, grad_scale)
+            L.check(L.sgd_step_guarded(pflat.data_ptr(), gflat.data_ptr(), self._state_bufs[0].data_ptr(), pflat.numel(), self.guard.block_ptr,
+                                       float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), torch.cuda.current_stream().cuda_stream),
+                    "sgd_step_guarded")
+            return
         L.check(L.sgd_step(pflat.data_ptr(), gflat.data_ptr(), self._state_bufs[0].data_ptr(), pflat.numel(), self._step, float(g["lr"]),
                            float(g["momentum"]), float(g["weight_decay"]), float(grad_scale), torch.cuda.current_stream().cuda_stream), "sgd_step")

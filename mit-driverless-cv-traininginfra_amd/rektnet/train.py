@@ -29,12 +29,26 @@ def _host_number(t):
 
 
 def train_model(model, output_uri, dataloader, loss_function, optimizer, scheduler, epochs, val_dataloader, intervals, input_size, num_kpt,
-                save_checkpoints, kpt_keys, study_name, evaluate_mode, progress=None, log=print, ring=64, stats=None):
+                save_checkpoints, kpt_keys, study_name, evaluate_mode, progress=None, log=print, ring=64, stats=None, guard=None,
+                clip_grad_norm=0.0, skip_nonfinite=False):
     """train_eval.py:45-113.  `progress(description)` gets every batch's description (default: dropped, a bar's text has no other
     reader), `log(line)` every printed line; `stats`, a dict, receives `host_waits` (per epoch, a list).  Batches already on the device
     (ConeCropBatches, SyntheticCones) are consumed as they are, host batches through `trainlog.prefetch`.  The heat-map targets are only
     moved for `l2_heatmap`-style losses by the loss function itself; `optimizer` may be any torch optimizer (FusedAdam for the headline
-    rate)."""
+    rate).
+
+    `guard`: the `mdcv.optim.GradGuard` to report on; default: the one the optimizer holds.  `clip_grad_norm` > 0 / `skip_nonfinite` (this
+    module has no command line: keywords, as `--clip_grad_norm` / `--skip_nonfinite` of mdcv.yolo.train) give a FusedAdam / FusedSGD
+    that holds no guard one with those settings; an optimizer that cannot take a guard is a TypeError.  With a guard, one line follows
+    each epoch's `Training:` line, from one read of the guard's counters after the epoch's wait:
+    `train Epoch: 3, grad norm max 41.2 mean 7.9, clipped 12, skipped 1 of 240 steps`.  Without one: no line, no read."""
+    if guard is None:
+        guard = getattr(optimizer, "guard", None)
+    if guard is None and (clip_grad_norm > 0 or skip_nonfinite):
+        from ..optim import GradGuard, _FlatOptimizer
+        if not isinstance(optimizer, _FlatOptimizer):
+            raise TypeError("clip_grad_norm / skip_nonfinite need a FusedAdam or FusedSGD: the guard runs inside their step()")
+        guard = optimizer.guard = GradGuard(max_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
     best_val_loss = float('inf')
     best_epoch = 0
     max_tolerance = 8
@@ -86,6 +100,8 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
         # total_loss[1]: the device's sum when the geo loss is a device tensor; the host's `0 + 0 + ...` (an int) when it never was
         total_loss = [sums[0], sums[1] + host_sum if any_device_geo else host_sum, sums[2]]
         log(format_epoch_line(total_loss, batch_num))
+        if guard is not None:
+            log(guard.summary_line("train", epoch))
         val_loc_loss, val_geo_loss, val_loss = eval_model(model=model, dataloader=val_dataloader, loss_function=loss_function,
                                                           input_size=input_size)
 

@@ -35,7 +35,7 @@ def format_step_line(label_prefix, epoch, i, n_batches, row):
     return statement
 
 
-def run_epoch(label_prefix, data_loader, num_steps, optimizer, model, epoch, num_epochs, step, log=print, ring=64, stats=None):
+def run_epoch(label_prefix, data_loader, num_steps, optimizer, model, epoch, num_epochs, step, log=print, ring=64, stats=None, guard=None):
     """train.py:49-93 with the reference's signature and return value `(epoch_losses, epoch_time_total, epoch_num_targets)`:
     `epoch_losses[j]` is the float sum of the steps' loss j and `epoch_num_targets` is `1e-12 + sum(count + 1e-12)`, both added on the
     device in the reference's order (bit for bit the reference's Python sums).  The `num_steps` break, `step[0] += 1` in "train" mode
@@ -51,7 +51,14 @@ def run_epoch(label_prefix, data_loader, num_steps, optimizer, model, epoch, num
     Batches that are already on the device are consumed as they are; host batches go through `trainlog.prefetch`.  The loop itself
     never waits for the GPU: `StepLog.host_waits` is 1 (the epoch's end) unless more than `ring` steps are in flight; a `stats` dict
     receives `host_waits` and `steps`.  (The model's own look at its bad-label flag behind each backward is unchanged;
-    `model.strict_targets = False` makes that a query too.)"""
+    `model.strict_targets = False` makes that a query too.)
+
+    `guard`: the `mdcv.optim.GradGuard` to report on; default: the one the optimizer holds (the optimizer, not this loop, runs it).  With a
+    guard, ONE more line follows the reference's lines, after the epoch's wait and from one read of the guard's counters:
+    `train Epoch: 3, grad norm max 41.2 mean 7.9, clipped 12, skipped 1 of 240 steps`.  Without a guard there is no such line and
+    no such read."""
+    if guard is None and optimizer is not None:
+        guard = getattr(optimizer, "guard", None)
     log(f"Model in {label_prefix} mode")
     device = next(model.parameters()).device
     n_batches = len(data_loader)
@@ -83,6 +90,8 @@ def run_epoch(label_prefix, data_loader, num_steps, optimizer, model, epoch, num
         raise
     slog.drain(block=True)
     sums = slog.sums()
+    if guard is not None:
+        log(guard.summary_line(label_prefix, epoch))
     if stats is not None:
         stats["host_waits"], stats["steps"] = slog.host_waits, slog.steps
     return sums[:7], time.time() - t1, sums[7]
@@ -101,7 +110,8 @@ def _output_uri(output_path, model_cfg):
 def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, output_path, dataset_path, num_epochs, num_steps,
           checkpoint_interval, augment_affine, augment_hsv, lr_flip, ud_flip, momentum, gamma, lr, weight_decay, vis_batch, data_aug, blur,
           salt, noise, contrast, sharpen, ts, debug_mode, upload_dataset, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
-          val_tolerance, min_epochs, log=print, device=None, precision=None, decode=None, num_workers=None, cache_bytes=None, state=None):
+          val_tolerance, min_epochs, log=print, device=None, precision=None, decode=None, num_workers=None, cache_bytes=None, state=None,
+          clip_grad_norm=0.0, skip_nonfinite=False):
     """train.py's `main` (train.py:95-259) with its keyword arguments, on the native pieces: `ImageLabelBatches` for both loaders (the
     reference's option mapping: the validation loader without augmentation, flips or shuffling; batch size 1 and no shuffle in
     `debug_mode`), `FusedAdam` / `FusedSGD`, `StepLR(step_size=1, gamma)` stepped at the top of every epoch as there, `run_epoch` above,
@@ -111,11 +121,14 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
     Beyond the reference's arguments: `log` (every line goes through it), `device`, `precision` (Darknet's), and the loaders' `decode`,
     `num_workers`, `cache_bytes`; `state`, a dict, receives the live `model`, `optimizer`, `epoch`, `step` and `val_losses` (the average
     validation loss of every check, in order) for a caller that wants more than the return value.  The ONNX export is not done: on the early stop the weights are saved as `<output>/<onnx_name>`, the
-    file the reference leaves there, and a line says that no ONNX file was written."""
+    file the reference leaves there, and a line says that no ONNX file was written.
+
+    `clip_grad_norm` > 0 and / or `skip_nonfinite` attach a `GradGuard` to the optimizer (global-norm clipping, dropping a step whose
+    gradient is not finite): each training epoch then logs one more line.  Both off (the default): no guard, nothing changes."""
     from .models import Darknet
     from .validate import validate
     from ..data.images import ImageLabelBatches
-    from ..optim import FusedAdam, FusedSGD
+    from ..optim import FusedAdam, FusedSGD, GradGuard
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
     log("Initializing model")
@@ -158,12 +171,13 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
     log("Loading weights")
     model.load_weights(weights_path, model.get_start_weight_dim())
     model = model.to(device, non_blocking=True)
+    guard = GradGuard(max_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite) if clip_grad_norm > 0 or skip_nonfinite else None
     if optimizer_pick == "Adam":
         log("Using Adam Optimizer")
-        optimizer = FusedAdam(model, lr=lr, weight_decay=weight_decay)
+        optimizer = FusedAdam(model, lr=lr, weight_decay=weight_decay, guard=guard)
     elif optimizer_pick == "SGD":
         log("Using SGD Optimizer")
-        optimizer = FusedSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        optimizer = FusedSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay, guard=guard)
     else:
         raise Exception(f"Invalid optimizer name: {optimizer_pick}")
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=1, gamma=gamma)
@@ -263,6 +277,8 @@ def _parser():
     parser.add_argument('--wh_loss', type=float, default=1.6, help='confidence loss for width and height')
     parser.add_argument('--no_object_loss', type=float, default=25, help='confidence loss for non-objectness')
     parser.add_argument('--object_loss', type=float, default=0.1, help='confidence loss for objectness')
+    parser.add_argument('--clip_grad_norm', type=float, default=0.0, help='clip the global gradient norm to this on the device (0 = off)')
+    add_bool_arg('skip_nonfinite', False, 'drop an optimizer step whose gradient holds a NaN or an Inf, decided on the device')
     return parser
 
 
@@ -276,7 +292,8 @@ def main(argv=None):
                  data_aug=opt.data_aug, blur=opt.augment_blur, salt=opt.augment_salt, noise=opt.augment_noise, contrast=opt.augment_contrast,
                  sharpen=opt.augment_sharpen, ts=opt.ts, debug_mode=opt.debug_mode, upload_dataset=opt.upload_dataset, xy_loss=opt.xy_loss,
                  wh_loss=opt.wh_loss, no_object_loss=opt.no_object_loss, object_loss=opt.object_loss, vanilla_anchor=opt.vanilla_anchor,
-                 val_tolerance=opt.val_tolerance, min_epochs=opt.min_epochs)
+                 val_tolerance=opt.val_tolerance, min_epochs=opt.min_epochs, clip_grad_norm=opt.clip_grad_norm,
+                 skip_nonfinite=opt.skip_nonfinite)
 
 
 if __name__ == '__main__':
