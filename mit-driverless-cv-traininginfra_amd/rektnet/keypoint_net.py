@@ -186,6 +186,7 @@ class KeypointNet(FlatParamsMixin, nn.Module):
         for blk in (self.res1, self.res2, self.res3, self.res4):
             rec, a = lower_block(plan, blk, a, B, H, W, bn_train, nbt, one_launch)
             recs.append(rec)
+        plan.recs = recs
         csh = ConvSpec(plan, self.out.weight, self.out.bias, 1, 0, 1, cin_pad=a.act.C)
         plan.emit_pack(csh, need_dgrad=True)
         lg = TNode(plan.new_act(B, H, W, K), name="logits")

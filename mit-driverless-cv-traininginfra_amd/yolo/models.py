@@ -375,6 +375,7 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
                 r.backward(plan)
             plan.mark_ready()
         plan.outs = cx.outs
+        plan.recs = recs
         return plan
 
     # ------------------------------------------------------------------------------------------ darknet .weights I/O
