@@ -547,6 +547,46 @@ int mdcv_adam_step_guarded(float* params, const float* grads, float* exp_avg, fl
 int mdcv_sgd_step_guarded(float* params, const float* grads, float* momentum_buf, long long n, const mdcv_grad_guard_block* block, float lr,
                           float momentum, float weight_decay, void* stream);
 
+/* ---- weight EMA (csrc/weight_ema.hip): an exponential moving average of the flat fp32 parameter buffer and of the BatchNorm
+ *      running statistics, kept in ONE shadow buffer.  Five enqueue-only entry points on the caller's stream; no process state; nothing
+ *      here waits for the GPU.  The state is the control block below (the caller zeroes it once).
+ *
+ *      mdcv_ema_advance: one thread.  apply = guard ? guard->apply : 1 (a NULL guard applies).  apply != 0: with t = block->updates,
+ *        d64 = min((double)decay, (1.0 + (double)t) / ((double)warmup + (double)t)) in double, d = (float)d64, omd = 1.0f - d;
+ *        block->d = d, block->omd = omd, block->apply = 1, block->updates = t + 1.  apply == 0: block->apply = 0, nothing else is
+ *        written.  0 <= decay < 1, warmup >= 1 (warmup == 1: d == decay from the first update).  No transcendental.
+ *
+ *      mdcv_ema_update: ema[i] = ema[i] + omd * (params[i] - ema[i]) for i < n: a subtraction, a product and a sum, each rounded to
+ *        fp32 on its own.  omd and apply are read from the block; block->apply == 0: every thread returns before it reads or writes
+ *        ema or params.  Any 16-byte aligned slice of the two buffers may be passed (as to mdcv_adam_step); any n >= 0.  params is read
+ *        with non-temporal loads: inside a training step this pass is its last reader.
+ *      mdcv_ema_update_segments: the same arithmetic, in ONE launch, over the rows of a device table: row r updates
+ *        ema[offset .. offset + length) from src[0 .. length).  src is any 4-byte aligned address; offset and length count elements.
+ *        A row that does not lie inside ema[0 .. ema_elems), or whose src is NULL, is left alone (checked on the device: the table lives there).
+ *
+ *      mdcv_ema_swap / mdcv_ema_swap_segments: exchange the 32-bit words of the two sides (no arithmetic: NaN payloads, signed zeros
+ *        and denormals pass unchanged), so that two calls restore every bit.  They read no block.
+ *
+ *      One grid pass of mdcv_ema_update / mdcv_ema_swap covers MDCV_EMA_MAX_GRID * MDCV_EMA_THREADS * 4 elements; longer ranges are
+ *      strided over. */
+#define MDCV_EMA_THREADS 256
+#define MDCV_EMA_MAX_GRID 2048
+typedef struct mdcv_ema_block {
+  long long updates;                              /* byte  0: updates applied so far */
+  float d, omd;                                   /* bytes 8, 12: the decay of the latest applied update and 1 - d */
+  int apply, reserved;                            /* bytes 16, 20; 24 bytes in all */
+} mdcv_ema_block;
+typedef struct mdcv_ema_segment {
+  const float* src;                               /* byte  0: the live tensor */
+  long long offset, length;                       /* bytes 8, 16: its place in the shadow buffer, in elements; 24 bytes in all */
+} mdcv_ema_segment;
+int mdcv_ema_advance(mdcv_ema_block* block, const mdcv_grad_guard_block* guard, float decay, long long warmup, void* stream);
+int mdcv_ema_update(float* ema, const float* params, long long n, const mdcv_ema_block* block, void* stream);
+int mdcv_ema_update_segments(float* ema, long long ema_elems, const mdcv_ema_segment* table, int n_segments, const mdcv_ema_block* block,
+                             void* stream);
+int mdcv_ema_swap(float* ema, float* params, long long n, void* stream);
+int mdcv_ema_swap_segments(float* ema, long long ema_elems, const mdcv_ema_segment* table, int n_segments, void* stream);
+
 /* ---- per-step bookkeeping of the training loops in one launch (csrc/train_log.hip; CVC-YOLOv3/train.py:54,63-64,74-90 ;
  *      RektNet/train_eval.py:74-78): what the loops read back with `.item()` every step stays on the device.
  *      losses: n_losses addresses ON THE HOST (copied into the launch), each a device pointer to ONE fp32 or NULL (= 0.0f: RektNet's

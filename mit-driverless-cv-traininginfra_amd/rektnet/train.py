@@ -5,6 +5,7 @@ message; validation is the batched `eval_model` (evaluate.py).  The three `.item
 csrc/train_log.hip): a batch's description is formatted when its row has landed on the host, the epoch's sums are added on the device in
 the reference's order, and the loop waits for the GPU once per epoch.  The ONNX branch (train_eval.py:92-99) is skipped with a notice.
 """
+import contextlib
 import os
 
 import torch
@@ -30,7 +31,7 @@ def _host_number(t):
 
 def train_model(model, output_uri, dataloader, loss_function, optimizer, scheduler, epochs, val_dataloader, intervals, input_size, num_kpt,
                 save_checkpoints, kpt_keys, study_name, evaluate_mode, progress=None, log=print, ring=64, stats=None, guard=None,
-                clip_grad_norm=0.0, skip_nonfinite=False):
+                clip_grad_norm=0.0, skip_nonfinite=False, ema=None, ema_decay=0.0, ema_warmup=10):
     """train_eval.py:45-113.  `progress(description)` gets every batch's description (default: dropped, a bar's text has no other
     reader), `log(line)` every printed line; `stats`, a dict, receives `host_waits` (per epoch, a list).  Batches already on the device
     (ConeCropBatches, SyntheticCones) are consumed as they are, host batches through `trainlog.prefetch`.  The heat-map targets are only
@@ -41,7 +42,14 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
     module has no command line: keywords, as `--clip_grad_norm` / `--skip_nonfinite` of mdcv.yolo.train) give a FusedAdam / FusedSGD
     that holds no guard one with those settings; an optimizer that cannot take a guard is a TypeError.  With a guard, one line follows
     each epoch's `Training:` line, from one read of the guard's counters after the epoch's wait:
-    `train Epoch: 3, grad norm max 41.2 mean 7.9, clipped 12, skipped 1 of 240 steps`.  Without one: no line, no read."""
+    `train Epoch: 3, grad norm max 41.2 mean 7.9, clipped 12, skipped 1 of 240 steps`.  Without one: no line, no read.
+
+    `ema`: the `mdcv.optim.WeightEMA` to validate with; default: the one the optimizer holds.  `ema_decay` > 0 (with `ema_warmup`) gives a
+    FusedAdam / FusedSGD that holds none a `WeightEMA(model, ema_decay, ema_warmup)`; an optimizer that cannot take one is a TypeError.
+    (An `ema` handed over beside an optimizer that does not hold it -- a torch optimizer -- is updated by this loop after each `step()`.)
+    With an EMA, `eval_model` runs with the averaged weights and BatchNorm statistics swapped in, so `val_loss`, the best
+    epoch and the tolerance describe the averaged model; the `.pt` checkpoint keeps the live `'model'` and gains `'ema'` (the EMA's
+    `state_dict()`).  Without one nothing changes."""
     if guard is None:
         guard = getattr(optimizer, "guard", None)
     if guard is None and (clip_grad_norm > 0 or skip_nonfinite):
@@ -49,6 +57,15 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
         if not isinstance(optimizer, _FlatOptimizer):
             raise TypeError("clip_grad_norm / skip_nonfinite need a FusedAdam or FusedSGD: the guard runs inside their step()")
         guard = optimizer.guard = GradGuard(max_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+    if ema is None:
+        ema = getattr(optimizer, "ema", None)
+    if ema is None and ema_decay > 0:
+        from ..optim import WeightEMA, _FlatOptimizer
+        if not isinstance(optimizer, _FlatOptimizer):
+            raise TypeError("ema_decay needs a FusedAdam or FusedSGD: the average is updated inside their step()")
+        ema = WeightEMA(model, decay=ema_decay, warmup=ema_warmup)
+        optimizer._take_ema(ema)
+    ema_by_hand = ema is not None and getattr(optimizer, "ema", None) is not ema      # a torch optimizer: the loop updates the average itself
     best_val_loss = float('inf')
     best_epoch = 0
     max_tolerance = 8
@@ -79,6 +96,8 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
                 loc_loss, geo_loss, loss = loss_function(output[0], output[1], y_hm_batch, y_points_batch)
                 loss.backward()
                 optimizer.step()
+                if ema_by_hand:
+                    ema.update()
                 if torch.is_tensor(geo_loss) and geo_loss.is_cuda:
                     any_device_geo = True
                     slog.record([loc_loss, geo_loss, loss], None, meta=None)
@@ -102,8 +121,9 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
         log(format_epoch_line(total_loss, batch_num))
         if guard is not None:
             log(guard.summary_line("train", epoch))
-        val_loc_loss, val_geo_loss, val_loss = eval_model(model=model, dataloader=val_dataloader, loss_function=loss_function,
-                                                          input_size=input_size)
+        with (ema.applied() if ema is not None else contextlib.nullcontext()):
+            val_loc_loss, val_geo_loss, val_loss = eval_model(model=model, dataloader=val_dataloader, loss_function=loss_function,
+                                                              input_size=input_size)
 
         # Position suggested by https://pytorch.org/docs/stable/optim.html#how-to-adjust-learning-rate
         scheduler.step()
@@ -124,6 +144,8 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
             checkpoint = {'epoch': epoch,
                           'model': model.state_dict(),
                           'optimizer': optimizer.state_dict()}
+            if ema is not None:
+                checkpoint['ema'] = ema.state_dict()
             torch.save(checkpoint, gs_pt_uri)
         if tolerance >= max_tolerance:
             log(f"Training is stopped due; loss no longer decreases. Epoch {best_epoch} is has the best validation loss.")

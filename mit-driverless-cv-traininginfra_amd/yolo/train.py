@@ -11,6 +11,7 @@ takes train.py's flags.  Not done here: the ONNX export behind the early stop (t
 renames them to, and a line says so), `vis_batch` drawing and `upload_dataset` (accepted and ignored, as the loader does).
 """
 import argparse
+import contextlib
 import os
 import time
 from datetime import datetime
@@ -111,7 +112,7 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
           checkpoint_interval, augment_affine, augment_hsv, lr_flip, ud_flip, momentum, gamma, lr, weight_decay, vis_batch, data_aug, blur,
           salt, noise, contrast, sharpen, ts, debug_mode, upload_dataset, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
           val_tolerance, min_epochs, log=print, device=None, precision=None, decode=None, num_workers=None, cache_bytes=None, state=None,
-          clip_grad_norm=0.0, skip_nonfinite=False):
+          clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0, ema_warmup=10):
     """train.py's `main` (train.py:95-259) with its keyword arguments, on the native pieces: `ImageLabelBatches` for both loaders (the
     reference's option mapping: the validation loader without augmentation, flips or shuffling; batch size 1 and no shuffle in
     `debug_mode`), `FusedAdam` / `FusedSGD`, `StepLR(step_size=1, gamma)` stepped at the top of every epoch as there, `run_epoch` above,
@@ -124,11 +125,17 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
     file the reference leaves there, and a line says that no ONNX file was written.
 
     `clip_grad_norm` > 0 and / or `skip_nonfinite` attach a `GradGuard` to the optimizer (global-norm clipping, dropping a step whose
-    gradient is not finite): each training epoch then logs one more line.  Both off (the default): no guard, nothing changes."""
+    gradient is not finite): each training epoch then logs one more line.  Both off (the default): no guard, nothing changes.
+
+    `ema_decay` > 0 attaches a `WeightEMA(model, ema_decay, ema_warmup)` to the optimizer.  The checkpoint block then runs
+    with the averaged weights and BatchNorm statistics swapped in: `<epoch>.weights`, the validation-loss epoch, `logs/result.txt`, the
+    stopping rule, `validate(...)` and the early stop's `<onnx_name>` file describe the averaged model; the live weights go to
+    `<epoch>.live.weights` (what a continued run loads), and one more line per checkpoint states the update count and the current decay
+    (one host read).  `evaluate=True` validates the weights it loaded.  0 (the default): no EMA, nothing changes."""
     from .models import Darknet
     from .validate import validate
     from ..data.images import ImageLabelBatches
-    from ..optim import FusedAdam, FusedSGD, GradGuard
+    from ..optim import FusedAdam, FusedSGD, GradGuard, WeightEMA
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
     log("Initializing model")
@@ -172,12 +179,14 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
     model.load_weights(weights_path, model.get_start_weight_dim())
     model = model.to(device, non_blocking=True)
     guard = GradGuard(max_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite) if clip_grad_norm > 0 or skip_nonfinite else None
+    ema = WeightEMA(model, decay=ema_decay, warmup=ema_warmup) if ema_decay > 0 else None
+    more = {} if ema is None else {"ema": ema}
     if optimizer_pick == "Adam":
         log("Using Adam Optimizer")
-        optimizer = FusedAdam(model, lr=lr, weight_decay=weight_decay, guard=guard)
+        optimizer = FusedAdam(model, lr=lr, weight_decay=weight_decay, guard=guard, **more)
     elif optimizer_pick == "SGD":
         log("Using SGD Optimizer")
-        optimizer = FusedSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay, guard=guard)
+        optimizer = FusedSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay, guard=guard, **more)
     else:
         raise Exception(f"Invalid optimizer name: {optimizer_pick}")
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=1, gamma=gamma)
@@ -198,33 +207,40 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
                       num_steps=num_steps, optimizer=optimizer, log=log)
             log('Completed epoch:  ' + str(epoch))
             if epoch % checkpoint_interval == 0 or epoch == num_epochs or step[0] >= num_steps:
-                model.save_weights(os.path.join(output_uri, "{epoch}.weights".format(epoch=epoch)))
-                with torch.no_grad():
-                    log("Calculating loss on validate data")
-                    epoch_losses, epoch_time_total, epoch_num_targets = run_epoch(
-                        label_prefix="validate", data_loader=validate_data_loader, epoch=epoch, model=model, num_epochs=num_epochs,
-                        num_steps=num_steps, optimizer=None, step=step, log=log)
-                    avg_epoch_loss = epoch_losses[0] / epoch_num_targets
-                    state["val_losses"].append(avg_epoch_loss)
-                    log('Average Validation Loss: {0:10.6f}'.format(avg_epoch_loss))
-                    if avg_epoch_loss > val_loss and epoch > min_epochs:
-                        val_loss_counter += 1
-                        log(f"Validation loss did not decrease for {val_loss_counter} consecutive check(s)")
-                    else:
-                        log("Validation loss decreased. Yay!!")
-                        val_loss_counter = 0
-                        val_loss = avg_epoch_loss
-                        os.makedirs("logs", exist_ok=True)
-                        with open("logs/result.txt", "w") as result:
-                            result.write(str(avg_epoch_loss))
-                    validate(dataloader=validate_data_loader, model=model, device=device, step=step[0], bbox_all=False,
-                             debug_mode=debug_mode)
-                    if val_loss_counter == val_tolerance:
-                        log("Validation loss stopped decreasing over the last " + str(val_tolerance) + " checkpoints, creating onnx file")
-                        save_weights_uri = os.path.join(output_uri, onnx_name)
-                        model.save_weights(save_weights_uri)
-                        log(f"ONNX export is not part of this build: darknet weights saved to {save_weights_uri}, no ONNX file written")
-                        break
+                if ema is not None:
+                    model.save_weights(os.path.join(output_uri, "{epoch}.live.weights".format(epoch=epoch)))
+                    log(ema.summary_line("train", epoch))
+                stop = False
+                with (ema.applied() if ema is not None else contextlib.nullcontext()):      # the averaged model, from here to the end of the block
+                    model.save_weights(os.path.join(output_uri, "{epoch}.weights".format(epoch=epoch)))
+                    with torch.no_grad():
+                        log("Calculating loss on validate data")
+                        epoch_losses, epoch_time_total, epoch_num_targets = run_epoch(
+                            label_prefix="validate", data_loader=validate_data_loader, epoch=epoch, model=model, num_epochs=num_epochs,
+                            num_steps=num_steps, optimizer=None, step=step, log=log)
+                        avg_epoch_loss = epoch_losses[0] / epoch_num_targets
+                        state["val_losses"].append(avg_epoch_loss)
+                        log('Average Validation Loss: {0:10.6f}'.format(avg_epoch_loss))
+                        if avg_epoch_loss > val_loss and epoch > min_epochs:
+                            val_loss_counter += 1
+                            log(f"Validation loss did not decrease for {val_loss_counter} consecutive check(s)")
+                        else:
+                            log("Validation loss decreased. Yay!!")
+                            val_loss_counter = 0
+                            val_loss = avg_epoch_loss
+                            os.makedirs("logs", exist_ok=True)
+                            with open("logs/result.txt", "w") as result:
+                                result.write(str(avg_epoch_loss))
+                        validate(dataloader=validate_data_loader, model=model, device=device, step=step[0], bbox_all=False,
+                                 debug_mode=debug_mode)
+                        if val_loss_counter == val_tolerance:
+                            log("Validation loss stopped decreasing over the last " + str(val_tolerance) + " checkpoints, creating onnx file")
+                            save_weights_uri = os.path.join(output_uri, onnx_name)
+                            model.save_weights(save_weights_uri)
+                            log(f"ONNX export is not part of this build: darknet weights saved to {save_weights_uri}, no ONNX file written")
+                            stop = True
+                if stop:
+                    break
         if evaluate:
             validate(dataloader=validate_data_loader, model=model, device=device, step=-1, bbox_all=False, debug_mode=debug_mode)
     finally:
@@ -279,6 +295,8 @@ def _parser():
     parser.add_argument('--object_loss', type=float, default=0.1, help='confidence loss for objectness')
     parser.add_argument('--clip_grad_norm', type=float, default=0.0, help='clip the global gradient norm to this on the device (0 = off)')
     add_bool_arg('skip_nonfinite', False, 'drop an optimizer step whose gradient holds a NaN or an Inf, decided on the device')
+    parser.add_argument('--ema_decay', type=float, default=0.0, help='validate and checkpoint an exponential moving average of the weights with this decay (0 = off)')
+    parser.add_argument('--ema_warmup', type=int, default=10, help='EMA warm-up: update t uses min(ema_decay, (1 + t) / (ema_warmup + t))')
     return parser
 
 
@@ -293,7 +311,7 @@ def main(argv=None):
                  sharpen=opt.augment_sharpen, ts=opt.ts, debug_mode=opt.debug_mode, upload_dataset=opt.upload_dataset, xy_loss=opt.xy_loss,
                  wh_loss=opt.wh_loss, no_object_loss=opt.no_object_loss, object_loss=opt.object_loss, vanilla_anchor=opt.vanilla_anchor,
                  val_tolerance=opt.val_tolerance, min_epochs=opt.min_epochs, clip_grad_norm=opt.clip_grad_norm,
-                 skip_nonfinite=opt.skip_nonfinite)
+                 skip_nonfinite=opt.skip_nonfinite, ema_decay=opt.ema_decay, ema_warmup=opt.ema_warmup)
 
 
 if __name__ == '__main__':
