@@ -135,8 +135,8 @@ int mdcv_bn_act_fwd(int dtype, const void* y1, int ld1, const float* s1, const f
 int mdcv_bn_act_bwd_reduce_ws_floats(int dtype, int M, int C, int nsums);
 /* partial rows -> statistics -> scale/shift (+ running stats) in ONE launch while rows <= 4096 (a workgroup owns 16 channels and
  * sums their rows itself); larger buffers are first folded to 64 rows IN PLACE by one more launch (no atomics; `partial` is the
- * caller's scratch and is consumed).  `accum` is unused (kept for the two-stage entry points mdcv_partial_reduce / mdcv_bn_finalize). */
-int mdcv_bn_stats_finalize(const float* partial, int rows, double* accum, double count, const float* gamma, const float* beta,
+ * caller's scratch and is consumed -- hence not `const`).  `accum` is unused (kept for the two-stage entry points mdcv_partial_reduce / mdcv_bn_finalize). */
+int mdcv_bn_stats_finalize(float* partial, int rows, double* accum, double count, const float* gamma, const float* beta,
                            float* running_mean, float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
                            float* invstd, int C, void* stream);
 /* mdcv_bn_act_bwd_reduce + mdcv_bn_bwd_finalize for one BatchNorm (y2 == NULL) or the fused residual pair, two launches in all. */
@@ -147,7 +147,7 @@ int mdcv_bn_act_bwd_reduce_finalize(int dtype, const void* dout, int ldd, const 
                                     const float* gamma2, float* dgamma2, float* dbeta2, float* cA2, float* cB2, float* cC2, void* stream);
 /* finalize for the fused data-gradient sums: rows x [2][C] partials (sum g, sum g*(y-mean)) -> dgamma, dbeta, cA, cB, cC
  * (more than 4096 rows are folded in place first, as above: `partial` is consumed) */
-int mdcv_bn_bwd_finalize_rows(const float* partial, int rows, int C, double count, const float* gamma, const float* mean,
+int mdcv_bn_bwd_finalize_rows(float* partial, int rows, int C, double count, const float* gamma, const float* mean,
                               const float* invstd, float* dgamma, float* dbeta, float* cA, float* cB, float* cC, void* stream);
 int mdcv_bn_act_bwd_reduce(int dtype, const void* dout, int ldd, const void* y1, int ld1, const float* s1, const float* b1,
                            const float* mean1, const float* invstd1, const void* y2, int ld2, const float* s2, const float* b2,

@@ -290,11 +290,11 @@ int mdcv_bn_finalize(double* accum, double count, const float* gamma, const floa
 }
 
 // conv-epilogue partial rows -> batch statistics -> scale / shift (+ running stats): one launch while the partial buffer is small
-int mdcv_bn_stats_finalize(const float* partial, int rows, double* accum, double count, const float* gamma, const float* beta,
+int mdcv_bn_stats_finalize(float* partial, int rows, double* accum, double count, const float* gamma, const float* beta,
                            float* running_mean, float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
                            float* invstd, int C, void* stream) {
   if (!partial || !accum || rows < 1 || !gamma || !beta || !scale || !shift || !mean || !invstd) return MDCV_EARG;
-  rows = fold_rows(const_cast<float*>(partial), rows, 2 * C, (hipStream_t)stream);      // (large buffers: folded in place first)
+  rows = fold_rows(partial, rows, 2 * C, (hipStream_t)stream);      // (large buffers: folded in place first)
   MDCV_CHECK_LAUNCH();
   ColFinArgs a = {};
   a.partial = partial; a.rows = rows; a.nsums = 2; a.C = C; a.count = count; a.gamma = gamma; a.beta = beta; a.rm = running_mean;
@@ -313,10 +313,10 @@ int mdcv_bn_bwd_finalize(double* accum, int kx, int nsums, int zero_after, doubl
   return MDCV_OK;
 }
 
-int mdcv_bn_bwd_finalize_rows(const float* partial, int rows, int C, double count, const float* gamma, const float* mean,
+int mdcv_bn_bwd_finalize_rows(float* partial, int rows, int C, double count, const float* gamma, const float* mean,
                               const float* invstd, float* dgamma, float* dbeta, float* cA, float* cB, float* cC, void* stream) {
   if (!partial || rows < 1 || !gamma || !mean || !invstd || !dgamma || !dbeta || !cA || !cB || !cC) return MDCV_EARG;
-  rows = fold_rows(const_cast<float*>(partial), rows, 2 * C, (hipStream_t)stream);
+  rows = fold_rows(partial, rows, 2 * C, (hipStream_t)stream);
   MDCV_CHECK_LAUNCH();
   ColFinArgs f = {};
   f.partial = partial; f.rows = rows; f.nsums = 2; f.C = C; f.count = count;
