@@ -1,6 +1,6 @@
-"""ctypes binding of libmdcv_hip.so.
+"""ctypes binding of libmdcv_hip.so, and of libmdcv_aug.so (device work outside the training step: `aug_lib()`).
 
-Prototypes are parsed from ``include/mdcv_hip.h`` so the header is the single source of truth for the C ABI.
+Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
 module fails loudly (the oracle under ``oracle/`` is test infrastructure and is never imported from here).
 """
@@ -12,6 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(ROOT, "include", "mdcv_hip.h")
 LIB_PATH = os.environ.get("MDCV_LIB") or os.path.join(_HERE, "libmdcv_hip.so")      # MDCV_LIB: another BUILD of the same library (timing ablations, scripts/wgrad_ab.py)
+
+AUG_HEADER = os.path.join(ROOT, "include", "mdcv_aug.h")
+AUG_LIB_PATH = os.path.join(_HERE, "libmdcv_aug.so")
 
 F32, BF16 = 0, 1
 
@@ -53,17 +56,18 @@ class MdcvError(RuntimeError):
 
 
 class _Lib:
-    def __init__(self):
-        if not os.path.exists(LIB_PATH):
+    def __init__(self, path=None, header=None, name="libmdcv_hip"):
+        path, header, self.name = path or LIB_PATH, header or HEADER, name
+        if not os.path.exists(path):
             raise MdcvError(
-                f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
+                f"{path} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"(or `make -C {os.path.join(_HERE, 'csrc')}`). There is no CPU fallback for the product path.")
         # torch bundles its own HIP runtime (torch/lib/libamdhip64.so, soname libamdhip64.so.7).  It must be in the process
         # BEFORE our library is dlopen'ed so that both bind to the same runtime instance; two runtimes in one process
         # do not share devices/streams (kernels launched through the second one fail with hipErrorNoDevice).
         import torch  # noqa: F401
-        self.cdll = ctypes.CDLL(LIB_PATH)
-        self.protos = parse_header()
+        self.cdll = ctypes.CDLL(path)
+        self.protos = parse_header(header)
         for name, (ret, argt, _) in self.protos.items():
             fn = getattr(self.cdll, name)       # AttributeError here == header/library mismatch
             fn.restype = ret
@@ -72,7 +76,7 @@ class _Lib:
 
     def check(self, rc, what=""):
         if rc != 0:
-            raise MdcvError(f"libmdcv_hip: {what} failed with code {rc}" + (" (bad argument)" if rc == -1 else " (hipError_t)"))
+            raise MdcvError(f"{self.name}: {what} failed with code {rc}" + (" (bad argument)" if rc == -1 else " (hipError_t)"))
 
 
 _lib = None
@@ -83,6 +87,17 @@ def lib():
     if _lib is None:
         _lib = _Lib()
     return _lib
+
+
+_aug = None
+
+
+def aug_lib():
+    """libmdcv_aug.so behind include/mdcv_aug.h: the same binding and the same `check` as `lib()`, loaded on first use"""
+    global _aug
+    if _aug is None:
+        _aug = _Lib(AUG_LIB_PATH, AUG_HEADER, "libmdcv_aug")
+    return _aug
 
 
 def require_gpu(t=None):

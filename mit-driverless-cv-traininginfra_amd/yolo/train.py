@@ -112,7 +112,7 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
           checkpoint_interval, augment_affine, augment_hsv, lr_flip, ud_flip, momentum, gamma, lr, weight_decay, vis_batch, data_aug, blur,
           salt, noise, contrast, sharpen, ts, debug_mode, upload_dataset, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
           val_tolerance, min_epochs, log=print, device=None, precision=None, decode=None, num_workers=None, cache_bytes=None, state=None,
-          clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0, ema_warmup=10):
+          clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0, ema_warmup=10, mosaic=0.0, mosaic_off_epochs=0):
     """train.py's `main` (train.py:95-259) with its keyword arguments, on the native pieces: `ImageLabelBatches` for both loaders (the
     reference's option mapping: the validation loader without augmentation, flips or shuffling; batch size 1 and no shuffle in
     `debug_mode`), `FusedAdam` / `FusedSGD`, `StepLR(step_size=1, gamma)` stepped at the top of every epoch as there, `run_epoch` above,
@@ -131,10 +131,16 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
     with the averaged weights and BatchNorm statistics swapped in: `<epoch>.weights`, the validation-loss epoch, `logs/result.txt`, the
     stopping rule, `validate(...)` and the early stop's `<onnx_name>` file describe the averaged model; the live weights go to
     `<epoch>.live.weights` (what a continued run loads), and one more line per checkpoint states the update count and the current decay
-    (one host read).  `evaluate=True` validates the weights it loaded.  0 (the default): no EMA, nothing changes."""
+    (one host read).  `evaluate=True` validates the weights it loaded.  0 (the default): no EMA, nothing changes.
+
+    `mosaic` > 0 wraps the TRAINING loader in `MosaicBatches(p=mosaic)`: each training image is, with that probability,
+    composed from four tiles of its batch on the device.  The validation loader never is.  The last `mosaic_off_epochs` epochs of
+    `num_epochs` run on the loader's own batches.  One more line follows each training epoch, after the epoch's wait and from one read of the
+    wrapper's counters.  0 (the default): no wrapper is constructed, nothing changes."""
     from .models import Darknet
     from .validate import validate
     from ..data.images import ImageLabelBatches
+    from ..data.mosaic import MosaicBatches
     from ..optim import FusedAdam, FusedSGD, GradGuard, WeightEMA
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
@@ -156,6 +162,8 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
                                           augment_hsv=augment_hsv, augment_affine=augment_affine, lr_flip=lr_flip, ud_flip=ud_flip,
                                           data_aug=data_aug, blur=blur, salt=salt, noise=noise, contrast=contrast, sharpen=sharpen,
                                           shuffle=(False if debug_mode else True), **extra)
+    if mosaic > 0:
+        train_data_loader = MosaicBatches(train_data_loader, p=mosaic)
     log("Num train images:  " + str(len(train_data_loader.dataset)))
     validate_data_loader = ImageLabelBatches(validate_uri, dataset_path, img_width, img_height, num_images=num_validate_images,
                                              augment_hsv=False, augment_affine=False, lr_flip=False, ud_flip=False, data_aug=False,
@@ -203,8 +211,12 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
             state["epoch"] = epoch
             scheduler.step()
             model.train()
+            if mosaic > 0:
+                train_data_loader.active = epoch <= num_epochs - mosaic_off_epochs
             run_epoch(label_prefix="train", data_loader=train_data_loader, epoch=epoch, step=step, model=model, num_epochs=num_epochs,
                       num_steps=num_steps, optimizer=optimizer, log=log)
+            if mosaic > 0:
+                log(train_data_loader.summary_line("train", epoch))
             log('Completed epoch:  ' + str(epoch))
             if epoch % checkpoint_interval == 0 or epoch == num_epochs or step[0] >= num_steps:
                 if ema is not None:
@@ -297,6 +309,8 @@ def _parser():
     add_bool_arg('skip_nonfinite', False, 'drop an optimizer step whose gradient holds a NaN or an Inf, decided on the device')
     parser.add_argument('--ema_decay', type=float, default=0.0, help='validate and checkpoint an exponential moving average of the weights with this decay (0 = off)')
     parser.add_argument('--ema_warmup', type=int, default=10, help='EMA warm-up: update t uses min(ema_decay, (1 + t) / (ema_warmup + t))')
+    parser.add_argument('--mosaic', type=float, default=0.0, help='compose each training image from four tiles of its batch with this probability, on the device (0 = off)')
+    parser.add_argument('--mosaic_off_epochs', type=int, default=0, help='train the last N of num_epochs epochs without mosaic')
     return parser
 
 
@@ -311,7 +325,8 @@ def main(argv=None):
                  sharpen=opt.augment_sharpen, ts=opt.ts, debug_mode=opt.debug_mode, upload_dataset=opt.upload_dataset, xy_loss=opt.xy_loss,
                  wh_loss=opt.wh_loss, no_object_loss=opt.no_object_loss, object_loss=opt.object_loss, vanilla_anchor=opt.vanilla_anchor,
                  val_tolerance=opt.val_tolerance, min_epochs=opt.min_epochs, clip_grad_norm=opt.clip_grad_norm,
-                 skip_nonfinite=opt.skip_nonfinite, ema_decay=opt.ema_decay, ema_warmup=opt.ema_warmup)
+                 skip_nonfinite=opt.skip_nonfinite, ema_decay=opt.ema_decay, ema_warmup=opt.ema_warmup, mosaic=opt.mosaic,
+                 mosaic_off_epochs=opt.mosaic_off_epochs)
 
 
 if __name__ == '__main__':
