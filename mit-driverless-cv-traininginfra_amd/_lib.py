@@ -1,4 +1,5 @@
-"""ctypes binding of libmdcv_hip.so, and of libmdcv_aug.so (device work outside the training step: `aug_lib()`).
+"""ctypes binding of libmdcv_hip.so, and of libmdcv_aug.so and libmdcv_kptaug.so (device work outside the training step: `aug_lib()`,
+DESIGN §29; `kptaug_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -15,6 +16,9 @@ LIB_PATH = os.environ.get("MDCV_LIB") or os.path.join(_HERE, "libmdcv_hip.so")  
 
 AUG_HEADER = os.path.join(ROOT, "include", "mdcv_aug.h")
 AUG_LIB_PATH = os.path.join(_HERE, "libmdcv_aug.so")
+
+KPTAUG_HEADER = os.path.join(ROOT, "include", "mdcv_kptaug.h")
+KPTAUG_LIB_PATH = os.path.join(_HERE, "libmdcv_kptaug.so")
 
 F32, BF16 = 0, 1
 
@@ -98,6 +102,17 @@ def aug_lib():
     if _aug is None:
         _aug = _Lib(AUG_LIB_PATH, AUG_HEADER, "libmdcv_aug")
     return _aug
+
+
+_kptaug = None
+
+
+def kptaug_lib():
+    """libmdcv_kptaug.so behind include/mdcv_kptaug.h: the same binding and `check` again, loaded on first use"""
+    global _kptaug
+    if _kptaug is None:
+        _kptaug = _Lib(KPTAUG_LIB_PATH, KPTAUG_HEADER, "libmdcv_kptaug")
+    return _kptaug
 
 
 def require_gpu(t=None):

@@ -31,7 +31,7 @@ def _host_number(t):
 
 def train_model(model, output_uri, dataloader, loss_function, optimizer, scheduler, epochs, val_dataloader, intervals, input_size, num_kpt,
                 save_checkpoints, kpt_keys, study_name, evaluate_mode, progress=None, log=print, ring=64, stats=None, guard=None,
-                clip_grad_norm=0.0, skip_nonfinite=False, ema=None, ema_decay=0.0, ema_warmup=10):
+                clip_grad_norm=0.0, skip_nonfinite=False, ema=None, ema_decay=0.0, ema_warmup=10, augment=None):
     """train_eval.py:45-113.  `progress(description)` gets every batch's description (default: dropped, a bar's text has no other
     reader), `log(line)` every printed line; `stats`, a dict, receives `host_waits` (per epoch, a list).  Batches already on the device
     (ConeCropBatches, SyntheticCones) are consumed as they are, host batches through `trainlog.prefetch`.  The heat-map targets are only
@@ -49,7 +49,17 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
     (An `ema` handed over beside an optimizer that does not hold it -- a torch optimizer -- is updated by this loop after each `step()`.)
     With an EMA, `eval_model` runs with the averaged weights and BatchNorm statistics swapped in, so `val_loss`, the best
     epoch and the tolerance describe the averaged model; the `.pt` checkpoint keeps the live `'model'` and gains `'ema'` (the EMA's
-    `state_dict()`).  Without one nothing changes."""
+    `state_dict()`).  Without one nothing changes.
+
+    `augment`: a dict of `mdcv.data.KeypointAugBatches` keywords (an empty one: its defaults) wraps `dataloader` -- the TRAINING loader,
+    never `val_dataloader` -- in one (affine, flip and colour on the device, one launch per batch); a `dataloader` that
+    already is a `KeypointAugBatches` is used as it is.  Either way one line follows each epoch's `Training:` line (behind the guard's, if
+    there is one), from one read of the wrapper's counters after the epoch's wait:
+    `train Epoch: 3, key-point augmentation: 951 of 1024 images augmented, rejected 73, passed through 0`.  Without: no line, no launch."""
+    from ..data.kptaug import KeypointAugBatches
+    if augment is not None and not isinstance(dataloader, KeypointAugBatches):
+        dataloader = KeypointAugBatches(dataloader, **augment)
+    kptaug = dataloader if isinstance(dataloader, KeypointAugBatches) else None
     if guard is None:
         guard = getattr(optimizer, "guard", None)
     if guard is None and (clip_grad_norm > 0 or skip_nonfinite):
@@ -121,6 +131,8 @@ def train_model(model, output_uri, dataloader, loss_function, optimizer, schedul
         log(format_epoch_line(total_loss, batch_num))
         if guard is not None:
             log(guard.summary_line("train", epoch))
+        if kptaug is not None:
+            log(kptaug.summary_line("train", epoch))
         with (ema.applied() if ema is not None else contextlib.nullcontext()):
             val_loc_loss, val_geo_loss, val_loss = eval_model(model=model, dataloader=val_dataloader, loss_function=loss_function,
                                                               input_size=input_size)
