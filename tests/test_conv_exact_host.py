@@ -47,10 +47,14 @@ def fuse10(t):
 PLAIN = ([(c, "fdw") for c in X.CONV_CASES + X.VARIANT_CASES + X.NARROW_CASES] +
          [(X.c3(c, bias=c == X.SHIFT_CASES[0]), "fd") for c in X.SHIFT_CASES] + [(X.c3(c), "fd") for c in X.SHIFT_2D + [X.SHIFT_W70]] +
          [(X.c3(c, dil=2), "fd") for c in X.SHIFT_DIL2] + [(X.c3(X.SHIFT_CASES[3]), "f"), (X.c3(X.SHIFT_2D[0]), "f")] +
-         [(c, "w") for c in [(3, 64, 26, 20, 64, 3, 1, 1, 1, False)] + [X.c3(c) for c in X.WGRAD_SHIFT_CASES]] +
-         [(stream10(c), "w") for c in X.WGRAD_STREAM_CASES + X.WGRAD_DIRECT_CASES] + [(ws2(c), "w") for c in X.WGRAD_S2_CASES] +
+         [(c, "w") for c in [(3, 64, 26, 20, 64, 3, 1, 1, 1, False)] + [X.c3(c) for c in X.WGRAD_SHIFT_CASES + X.WGRAD_KWSHARED_CASES]] +
+         [(pc["geom"], pc["run"].replace("b", "")) for pc in X.PROD_CASES if pc["run"] != "b"] +
+         [(stream10(c), "w") for c in X.WGRAD_STREAM_CASES + X.WGRAD_DIRECT_CASES + X.WGRAD_STREAM_PROD] + [(ws2(c), "w") for c in X.WGRAD_S2_CASES] +
          [((B, 3, H, W, 16, 7, 1, 3, 1, False), "w") for B, H, W in X.STEM_CASES] + [(X.c3(c), "d") for c in X.SHIFT_WIDE_DGRAD])
-FUSED = ([(s2(c), (1,)) for c in X.S2_CASES] + [(s2d(c), (1,)) for c in X.S2D_CASES] + [(X.FUSE1X1_CASE, (1,))] + [(fuse10(c), (0, 1, 2)) for c in X.FUSE_CASES])
+FUSED = ([(s2(c), (1,)) for c in X.S2_CASES] + [(s2d(c), (1,)) for c in X.S2D_CASES] + [(X.FUSE1X1_CASE, (1,))] + [(fuse10(c), (0, 1, 2)) for c in X.FUSE_CASES] +
+         [(pc["geom"], (1,)) for pc in X.PROD_CASES if "b" in pc["run"]])
+# the dense grids (helpers/conv_exact.py DENSE_CASES, under their own cap): forward of the two forward cases, data gradient plain / + addsrc / fused of the third
+DENSE = [(X.DENSE_FWD, "f"), (X.DENSE_FWD256, "f"), (X.DENSE_DGRAD, "d")]
 
 
 @pytest.mark.parametrize("case,what", PLAIN, ids=str)
@@ -58,6 +62,16 @@ def test_preconditions_plain(case, what):
     B, Ci, H, W, Co, k, s, p, d, bias = case
     c = X.gen_case(X.seed_of(case), B, Ci, H, W, Co, k, s, p, d, bias)
     X.check_exact_preconditions(X.conv_conditions(c, fwd="f" in what, dgrad="d" in what, wgrad="w" in what))
+
+
+@pytest.mark.parametrize("case,what", DENSE, ids=str)
+def test_preconditions_dense(case, what):
+    assert X.MACS_CAP < X.macs(X.c3(case)) <= X.DENSE_MACS_CAP and [c for c, _ in DENSE] == X.DENSE_CASES
+    c = X.dense_refs(case)
+    X.check_exact_preconditions(X.conv_conditions(c, fwd="f" in what, dgrad="d" in what, wgrad=False))
+    if what == "d":
+        X.check_exact_preconditions(X.fused_dgrad_conditions(c, codes=(1,), adds=(True,)))
+        X.check_exact_preconditions({"dx": ("bf16", c["_dx"])})
 
 
 @pytest.mark.parametrize("case,codes", FUSED, ids=str)
@@ -71,16 +85,21 @@ def test_preconditions_wgrad_bnapply(case):
     X.check_exact_preconditions(X.bnapply_conditions(case))
 
 
-@pytest.mark.parametrize("table,case", [(t, c) for t in ("PW_CASES", "PWB_CASES", "FIRST_CASES", "AFFINE_CASES") for c in getattr(X, t)], ids=str)
+@pytest.mark.parametrize("table,case", [(t, c) for t in ("PW_CASES", "PW_PROD_CASES", "PWB_CASES", "PWB_PROD_CASES", "FIRST_CASES", "AFFINE_CASES") for c in getattr(X, t)] +
+                         [("AFFINE_PROD_CASES", c) for c, _ in X.AFFINE_PROD_CASES], ids=str)
 def test_preconditions_block_forms(table, case):
-    refs = {"PW_CASES": X.pw_refs, "PWB_CASES": X.pwb_refs, "FIRST_CASES": X.first_refs, "AFFINE_CASES": X.affine_refs}[table]
+    refs = {"PW_CASES": X.pw_refs, "PW_PROD_CASES": X.pw_refs, "PWB_CASES": X.pwb_refs, "PWB_PROD_CASES": X.pwb_refs, "AFFINE_PROD_CASES": X.affine_refs, "FIRST_CASES": X.first_refs, "AFFINE_CASES": X.affine_refs}[table]
     X.check_exact_preconditions(refs(case)["cond"])
 
 
 def test_reference_cap_and_generator_rules():
     for case, _ in PLAIN:
+        if case in [pc["geom"] for pc in X.PROD_CASES if pc.get("dense")]:
+            continue
         listed = case in [stream10(X.WGRAD_DIRECT_CASES[1]), X.c3(X.SHIFT_WIDE_DGRAD[0])]        # the two 512 -> 1024 layers at 13 x 13 (3.2e9)
         assert X.macs(case) <= X.MACS_CAP or listed, case
+    for pc in X.PROD_CASES:                                  # the dense 128-wide grids sit under their own, named cap; everything else under MACS_CAP
+        assert X.prod_macs_ok(pc) and (not pc.get("dense") or X.macs(pc["geom"]) > X.MACS_CAP), pc["id"]
     c = X.conv_case(X.CONV_CASES[9])
     assert set(c["x"].unique().tolist()) == {-2.0, -1.0, 0.0, 1.0, 2.0} and set(c["w"].unique().tolist()) == {-1.0, 0.0, 1.0}
     assert float(c["addsrc"].abs().max()) == 4.0
