@@ -4,6 +4,9 @@ detect.py) binds the MI355X-native classes.  The directory holds this one module
 `validate.py` -- so `from utils.datasets import ImageLabelDataset`, `from utils.utils import model_info, Logger, ...`,
 `from utils.nms import nms` and `import validate` (train.py:20-22) keep resolving to the reference's own files.
 
+`Darknet` keeps the reference's signature; behind it, keyword-only, `cls_loss=` / `cls_mode=` switch on the class loss the reference
+multiplies by 0.
+
 `use_hip_postprocessing()` optionally swaps the reference's per-image NMS loop for the batched HIP one, in whatever `utils.nms`
 module is importable (call it before `import validate`).
 """

@@ -1,5 +1,5 @@
-"""ctypes binding of libmdcv_hip.so, and of libmdcv_aug.so and libmdcv_kptaug.so (device work outside the training step: `aug_lib()`,
-DESIGN §29; `kptaug_lib()`).
+"""ctypes binding of libmdcv_hip.so, of libmdcv_aug.so and libmdcv_kptaug.so (device work outside the training step: `aug_lib()`,
+DESIGN §29; `kptaug_lib()`) and of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -19,6 +19,11 @@ AUG_LIB_PATH = os.path.join(_HERE, "libmdcv_aug.so")
 
 KPTAUG_HEADER = os.path.join(ROOT, "include", "mdcv_kptaug.h")
 KPTAUG_LIB_PATH = os.path.join(_HERE, "libmdcv_kptaug.so")
+
+CLS_HEADER = os.path.join(ROOT, "include", "mdcv_cls.h")
+CLS_LIB_PATH = os.path.join(_HERE, "libmdcv_cls.so")
+CLS_MODES = {"ce": 0, "bce": 1}                  # include/mdcv_cls.h MDCV_CLS_CE / MDCV_CLS_BCE
+CLS_ERR_WORD = 3                                 # int32 index of the err word in a class workspace (MDCV_CLS_ERR_WORD)
 
 F32, BF16 = 0, 1
 
@@ -113,6 +118,24 @@ def kptaug_lib():
     if _kptaug is None:
         _kptaug = _Lib(KPTAUG_LIB_PATH, KPTAUG_HEADER, "libmdcv_kptaug")
     return _kptaug
+
+
+_cls = None
+
+
+def cls_lib():
+    """libmdcv_cls.so behind include/mdcv_cls.h: the same binding and `check`, loaded on first use -- by a model built
+    with cls_loss != 0 only"""
+    global _cls
+    if _cls is None:
+        _cls = _Lib(CLS_LIB_PATH, CLS_HEADER, "libmdcv_cls")
+    return _cls
+
+
+def cls_mode(name):
+    if name not in CLS_MODES:
+        raise ValueError(f"cls_mode must be one of {sorted(CLS_MODES)}, got {name!r}")
+    return CLS_MODES[name]
 
 
 def require_gpu(t=None):

@@ -7,37 +7,9 @@
 // mul+add pair is fused into an fma.
 //
 // logits are NHWC: channel = a*(5+C) + attr, channel stride ldc (pad channels ignored on read, zero on write).
-#include "common.h"
+#include "yolo_head_core.h"   // HeadGeom, assign_row, sigmoidf_, head_ws: shared with csrc/yolo_cls.hip
 
 namespace {
-
-struct HeadGeom {
-  int B, T, A, C, Gh, Gw, ldc;
-  float thresh;
-};
-
-// row (b,t) -> source row (padding rows take row 0, utils.py:223-228), grid coords, best anchor, "any IoU > thresh"
-__device__ __forceinline__ void assign_row(const float* __restrict__ tg, const float* __restrict__ anchors, const HeadGeom& g, int b, int t,
-                                           int& src, int& gi, int& gj, int& best, bool& over, float& gx, float& gy, float& gw, float& gh) {
-  const float* r = tg + ((size_t)b * g.T + t) * 5;
-  float s = r[0]; s = s + r[1]; s = s + r[2]; s = s + r[3]; s = s + r[4];       // utils.py:210
-  src = s > 0.f ? t : 0;
-  const float* q = tg + ((size_t)b * g.T + src) * 5;
-  gx = q[1] * (float)g.Gw; gy = q[2] * (float)g.Gh; gw = q[3] * (float)g.Gw; gh = q[4] * (float)g.Gh;   // :213-216
-  gi = (int)gx; gj = (int)gy;                                                    // :219-220 truncation
-  best = 0; over = false;
-  float best_iou = -1.f;
-  for (int a = 0; a < g.A; ++a) {                                               // :236-240 via bbox_iou :178-191
-    const float aw = anchors[2 * a], ah = anchors[2 * a + 1];
-    const float ix = fminf(gw, aw) - 0.f + 1.f, iy = fminf(gh, ah) - 0.f + 1.f;
-    const float inter = fmaxf(ix, 0.f) * fmaxf(iy, 0.f);
-    const float a1 = (gw - 0.f + 1.f) * (gh - 0.f + 1.f);
-    const float a2 = (aw - 0.f + 1.f) * (ah - 0.f + 1.f);
-    const float iou = inter / (a1 + a2 - inter + 1e-12f);
-    if (iou > g.thresh) over = true;
-    if (iou > best_iou) { best_iou = iou; best = a; }                            // :257 first max wins
-  }
-}
 
 // owner[b,a,j,i] = highest t assigned to the cell (sequential index_put => last writer wins), ignore[j,i] batch-wide
 __global__ void yolo_assign_kernel(const float* __restrict__ tg, const float* __restrict__ anchors, HeadGeom g, int* __restrict__ owner,
@@ -58,15 +30,6 @@ __global__ void yolo_assign_kernel(const float* __restrict__ tg, const float* __
 }
 
 static unsigned grid_for(long long n) { long long g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-
-// 1 / (1 + expf(-x)) wherever expf(-x) is finite.  From x = -88.8 down expf(-x) is inf and the quotient 0, while the true value
-// e^x / (1 + e^x) = e^x (1 + e^x rounds to 1) is still a (denormal) fp32 number: with 0, BCE(p, 1) clamps at 100 instead of -x and its
-// gradient vanishes.  Every logit above -88.8 keeps the bits it always had, so a training run without such logits is unchanged.
-// Used by the loss, gradient and decode kernels only: the assignment path has no sigmoid.
-__device__ __forceinline__ float sigmoidf_(float x) {
-  const float e = expf(-x);
-  return e == INFINITY ? expf(x) : 1.f / (1.f + e);
-}
 
 // out[0] += head loss ; out[1..6] += (x,y,w,h,obj,noobj) parts (models.py:199-211,332,338).  A launch of its own: folding it into the
 // last block of the loss kernel needs an agent-scope fence per block, and on eight L2s that tripled the loss kernel (11 -> 33 us).
@@ -149,7 +112,8 @@ struct GradArgs {
   float xy_loss, wh_loss, obj_loss, noobj_loss;
 };
 
-// d(loss)/d(logits) of one (pixel, channel) element; class channels and pad channels are exact zeros
+// d(loss)/d(logits) of one (pixel, channel) element; class channels and pad channels are exact zeros (the opt-in
+// class loss, csrc/yolo_cls.hip, overwrites the class channels of owned cells behind this pass)
 template <typename T>
 __device__ __forceinline__ float yolo_grad_elem(const GradArgs& a, const T* __restrict__ lg, long long pix, int ch, float nM, float nN) {
   const HeadGeom& g = a.g;
@@ -362,10 +326,10 @@ int mdcv_yolo_head_train(int dtype, const void* logits, int ldc, void* dlogits, 
   if (Gh > 4095 || Gw > 4095 || A > 127 || A * (5 + C) > Cpad) return MDCV_EARG;
   hipStream_t st = (hipStream_t)stream;
   HeadGeom g{B, T, A, C, Gh, Gw, ldc, thresh};
-  const long long cells = (long long)B * A * Gh * Gw;
-  long long ints = cells + (long long)Gh * Gw + 2; ints = (ints + 1) & ~1LL;
-  int* owner = (int*)workspace; int* ignore = owner + cells; int* err = ignore + (long long)Gh * Gw;
-  double* acc = (double*)((int*)workspace + ints);
+  const HeadWs w = head_ws(workspace, B, A, Gh, Gw);
+  const long long cells = w.cells, ints = w.ints;
+  int* owner = w.owner; int* ignore = w.ignore; int* err = w.err;
+  double* acc = w.acc;
   MDCV_LAUNCH(yolo_init_kernel, dim3(grid_for(ints + 16)), dim3(256), 0, st, owner, cells, ints + 16);
   MDCV_CHECK_LAUNCH();
   MDCV_LAUNCH(yolo_assign_kernel, dim3(grid_for((long long)B * T)), dim3(256), 0, st, targets, anchors_scaled, g, owner, ignore, (int*)nullptr, err);
@@ -394,10 +358,9 @@ int mdcv_yolo_head_grad(int dtype, const void* logits, int ldc, void* dlogits, i
   if (A * (5 + C) > Cpad) return MDCV_EARG;
   hipStream_t st = (hipStream_t)stream;
   HeadGeom g{B, T, A, C, Gh, Gw, ldc, thresh};
-  const long long cells = (long long)B * A * Gh * Gw;
-  long long ints = cells + (long long)Gh * Gw + 2; ints = (ints + 1) & ~1LL;
-  int* owner = (int*)workspace; int* ignore = owner + cells;
-  double* acc = (double*)((int*)workspace + ints);
+  const HeadWs w = head_ws(workspace, B, A, Gh, Gw);
+  int* owner = w.owner; int* ignore = w.ignore;
+  double* acc = w.acc;
   GradArgs ga{logits, dlogits, targets, anchors_scaled, owner, ignore, acc, gscale, g, ldd, Cpad, xy_loss, wh_loss, obj_loss, noobj_loss};
   if (dtype == MDCV_BF16) launch_yolo_grad<bf16_t>(ga, st);
   else if (dtype == MDCV_F32) launch_yolo_grad<float>(ga, st);

@@ -380,7 +380,16 @@ def lower_yolo(cx, i, d):
     plan.call(plan.fwd, L.yolo_head_train, plan.dtype, lg.act.ptr, lg.act.ldc, None, 0, lg.act.C, plan.targets.data_ptr(),
               anchors.data_ptr(), *geo, ws.data_ptr(), plan.out7.data_ptr(), None)
     plan.watch_head(ws, B, A, Gh, Gw)
-    return YoloHead(lg, anchors, ws, geo)
+    cls = None
+    if yl.cls_loss != 0:                                     # opt-in class loss (csrc/yolo_cls.hip): behind the head, same stream
+        K = _lib.cls_lib()
+        cls = (float(yl.ignore_thres), _lib.cls_mode(yl.cls_mode), float(yl.cls_loss))
+        cws = torch.zeros(int(K.yolo_cls_workspace_bytes()), dtype=torch.uint8, device=plan.device)
+        plan.keep.append(cws)
+        plan.call(plan.fwd, K.yolo_cls_loss, plan.dtype, lg.act.ptr, lg.act.ldc, plan.targets.data_ptr(), anchors.data_ptr(), *geo[:6], *cls,
+                  ws.data_ptr(), cws.data_ptr(), plan.out7.data_ptr(), plan.cls_out.data_ptr())
+        plan.watch_cls(cws)
+    return YoloHead(lg, anchors, ws, geo, cls)
 
 
 @dataclass
@@ -389,6 +398,7 @@ class YoloHead:
     anchors: torch.Tensor
     ws: torch.Tensor            # head workspace (csrc/yolo_head.hip)
     geo: tuple
+    cls: tuple = None           # (thresh, mode, cls_loss) of the class loss, or None: off
 
     def backward(self, plan):
         lg = self.lg
@@ -396,6 +406,9 @@ class YoloHead:
         assert add is None
         plan.call(plan.bwd, plan.L.yolo_head_grad, plan.dtype, lg.act.ptr, lg.act.ldc, out.ptr, out.ldc, out.C, plan.targets.data_ptr(),
                   self.anchors.data_ptr(), *self.geo, self.ws.data_ptr(), plan.gscale.data_ptr())
+        if self.cls is not None:                             # overwrites the class channels of the owned cells in the plane just written
+            plan.call(plan.bwd, _lib.cls_lib().yolo_cls_grad, plan.dtype, lg.act.ptr, lg.act.ldc, out.ptr, out.ldc, out.C,
+                      plan.targets.data_ptr(), self.anchors.data_ptr(), *self.geo[:6], *self.cls, self.ws.data_ptr(), plan.gscale.data_ptr())
 
 
 FORWARD = {"convolutional": lower_convolutional, "shortcut": lower_shortcut, "maxpool": lower_maxpool, "upsample": lower_upsample,

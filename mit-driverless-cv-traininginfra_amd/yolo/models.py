@@ -12,7 +12,8 @@ fused YOLO heads — and the whole backward is one autograd node that runs the m
 fp32 master parameters (OIHW) and BatchNorm buffers.  There is no CPU fallback.
 
 Extra (non-reference) knobs: `precision=` ctor kwarg or env MDCV_PRECISION in {"bf16" (default), "fp32"};
-env MDCV_GRAPH=1 replays the plan through hipGraphs.
+env MDCV_GRAPH=1 replays the plan through hipGraphs; `cls_loss=` / `cls_mode=` ctor kwargs switch the class loss on (the reference multiplies
+it by a hard-coded 0, models.py:203-205; csrc/yolo_cls.hip), default 0 = off: nothing of it is built, loaded or launched.
 """
 from __future__ import division
 
@@ -45,7 +46,7 @@ class EmptyLayer(nn.Module):
     """Placeholder module for 'route' and 'shortcut' sections (keeps module_list indices aligned with the cfg)."""
 
 
-def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor):
+def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, *, cls_loss=0.0, cls_mode="ce"):
     """cfg sections -> (hyperparams, nn.ModuleList).  Naming / ordering rules follow reference models.py:15-110 so that
     state_dict keys and `.weights` traversal (`module[0]` conv, `module[1]` BN) stay compatible."""
     hyper = module_defs.pop(0)
@@ -95,7 +96,7 @@ def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, v
             seq.add_module("shortcut_%d" % i, EmptyLayer())
         elif kind == "yolo":
             seq.add_module("yolo_%d" % i, YOLOLayer([anchors_all[v] for v in masks[head]], n_cls, img_h, img_w, ignore, activation,
-                                                    xy_loss, wh_loss, object_loss, no_object_loss))
+                                                    xy_loss, wh_loss, object_loss, no_object_loss, cls_loss=cls_loss, cls_mode=cls_mode))
             head += 1
             filters = channels[-1]
         else:
@@ -129,19 +130,33 @@ class _YoloHeadFn(torch.autograd.Function):
                                   out7.data_ptr(), None, st), "yolo_head_train")
         if _CHECK_TARGETS and int(_head_err_view(ws, B, A, Gh, Gw).item()):
             raise IndexError(_BAD_TARGET_MSG)
-        ctx.saved = (lg, tg, anchors, ws, geo, cp, ch)
+        cls = None
+        if layer.cls_loss != 0:                                   # the class loss rides behind the head, on the same stream
+            K = _lib.cls_lib()
+            cls = (float(layer.ignore_thres), _lib.cls_mode(layer.cls_mode), float(layer.cls_loss))
+            cws = torch.zeros(int(K.yolo_cls_workspace_bytes()), dtype=torch.uint8, device=dev)
+            layer.loss_cls = torch.zeros(1, dtype=torch.float32, device=dev)
+            K.check(K.yolo_cls_loss(_lib.F32, lg.data_ptr(), cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], *cls, ws.data_ptr(),
+                                    cws.data_ptr(), out7.data_ptr(), layer.loss_cls.data_ptr(), st), "yolo_cls_loss")
+            if _CHECK_TARGETS and int(_cls_err_view(cws).item()):
+                raise IndexError(_BAD_CLASS_MSG)
+        ctx.saved = (lg, tg, anchors, ws, geo, cp, ch, cls)
         return out7
 
     @staticmethod
     def backward(ctx, gout):
         L = _lib.lib()
-        lg, tg, anchors, ws, geo, cp, ch = ctx.saved
+        lg, tg, anchors, ws, geo, cp, ch, cls = ctx.saved
         B, Gh, Gw = geo[0], geo[4], geo[5]
         st = torch.cuda.current_stream().cuda_stream
         g = gout.contiguous()
         dl = torch.empty_like(lg)
         L.check(L.yolo_head_grad(_lib.F32, lg.data_ptr(), cp, dl.data_ptr(), cp, cp, tg.data_ptr(), anchors.data_ptr(), *geo, ws.data_ptr(),
                                  g.data_ptr(), st), "yolo_head_grad")
+        if cls is not None:
+            K = _lib.cls_lib()
+            K.check(K.yolo_cls_grad(_lib.F32, lg.data_ptr(), cp, dl.data_ptr(), cp, cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], *cls,
+                                    ws.data_ptr(), g.data_ptr(), st), "yolo_cls_grad")
         ds = torch.empty(B, ch, Gh, Gw, dtype=torch.float32, device=lg.device)
         L.check(L.nhwc_to_nchw(_lib.F32, dl.data_ptr(), cp, ds.data_ptr(), B, ch, Gh, Gw, st), "nhwc_to_nchw")
         return None, ds, None
@@ -149,11 +164,16 @@ class _YoloHeadFn(torch.autograd.Function):
 
 class YOLOLayer(nn.Module):
     """Detection head.  ctor argument order as in the reference (note object_loss before no_object_loss, models.py:121).
-    forward(sample, targets) -> (loss, tensor(6 parts: x,y,w,h,obj,noobj)) ; forward(sample) -> [B, A*G*G, 5+C]."""
+    forward(sample, targets) -> (loss, tensor(6 parts: x,y,w,h,obj,noobj)) ; forward(sample) -> [B, A*G*G, 5+C].
+    cls_loss != 0 adds the class loss (cls_mode 'ce': the reference's cross entropy over the class sigmoids; 'bce': independent logistic
+    classifiers) to `loss`; its value is `self.loss_cls` (a one-float device tensor) after a forward with targets."""
 
     def __init__(self, anchors, num_classes, img_height, img_width, build_targets_ignore_thresh, conv_activation, xy_loss, wh_loss,
-                 object_loss, no_object_loss):
+                 object_loss, no_object_loss, *, cls_loss=0.0, cls_mode="ce"):
         super().__init__()
+        _lib.cls_mode(cls_mode)                                    # (ValueError for an unknown name, also when cls_loss == 0)
+        self.cls_loss, self.cls_mode = float(cls_loss), cls_mode
+        self.loss_cls = None
         self.anchors = anchors
         self.num_anchors = len(anchors)
         self.num_classes = num_classes
@@ -212,6 +232,15 @@ _BAD_TARGET_MSG = ("index out of range in build_targets: a target has cx >= 1.0 
                    "raises IndexError at utils/utils.py:262")
 
 
+_BAD_CLASS_MSG = ("index out of range in build_targets: a target's class id is outside [0, classes) (the reference raises IndexError at "
+                  "utils/utils.py:271 for an id >= classes and wraps a negative one)")
+
+
+def _cls_err_view(cws):
+    """the int32 err word of a class-loss workspace (include/mdcv_cls.h MDCV_CLS_ERR_WORD)"""
+    return cws.view(torch.int32)[_lib.CLS_ERR_WORD:_lib.CLS_ERR_WORD + 1]
+
+
 def _head_err_view(ws, B, A, Gh, Gw):
     """the int32 `err` word of a YOLO head workspace (csrc/yolo_head.hip: owner[B*A*Gh*Gw] | ignore[Gh*Gw] | err)"""
     return ws.view(torch.int32)[B * A * Gh * Gw + Gh * Gw:B * A * Gh * Gw + Gh * Gw + 1]
@@ -224,6 +253,11 @@ class _YoloPlan(netplan._NetPlan):
 
     def watch_head(self, ws, B, A, Gh, Gw):
         self.err_views = tuple(self.err_views) + (_head_err_view(ws, B, A, Gh, Gw),)
+
+    def watch_cls(self, cws):
+        """the class err word of one head joins the same one-step-late check (it says so in its message)"""
+        self.cls_err_at = tuple(getattr(self, "cls_err_at", ())) + (len(self.err_views),)
+        self.err_views = tuple(self.err_views) + (_cls_err_view(cws),)
 
     def check_targets(self, block=True):
         """Raises IndexError if the targets of the LAST forward through this plan held a centre coordinate >= 1.0 (the reference's
@@ -241,7 +275,8 @@ class _YoloPlan(netplan._NetPlan):
         self._err_event = None
         ev.synchronize()
         if bool(self._err_host.any()):
-            raise IndexError(_BAD_TARGET_MSG)
+            bad_cls = any(int(self._err_host[k]) for k in getattr(self, "cls_err_at", ()))
+            raise IndexError(_BAD_CLASS_MSG if bad_cls else _BAD_TARGET_MSG)
 
     def before_forward(self, targets):
         if targets is not None:
@@ -260,10 +295,14 @@ class _YoloPlan(netplan._NetPlan):
 class Darknet(netplan.FlatParamsMixin, nn.Module):
     """YOLOv3 object detection model (reference: CVC-YOLOv3/models.py:222-422)."""
 
-    def __init__(self, config_path, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, precision=None):
+    def __init__(self, config_path, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, precision=None, *, cls_loss=0.0,
+                 cls_mode="ce"):
         super().__init__()
         self.module_defs = parse_model_config(config_path)
-        self.hyperparams, self.module_list = create_modules(self.module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor)
+        self.hyperparams, self.module_list = create_modules(self.module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
+                                                            cls_loss=cls_loss, cls_mode=cls_mode)
+        self.cls_loss, self.cls_mode = float(cls_loss), cls_mode
+        self.loss_cls = None             # after a forward with targets and cls_loss != 0: the class part of out[0], summed over the heads (device, 1 float)
         h = self.hyperparams
         self.img_width, self.img_height = int(h["width"]), int(h["height"])
         self.onnx_height = int(h["onnx_height"])
@@ -331,6 +370,7 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
         if targets is None:
             plan.run_forward(x)
             return plan.eval_out.clone()
+        self.loss_cls = plan.cls_out         # (the plan's own tensor: it holds this forward's value until the next forward through the plan)
         if torch.is_grad_enabled() and plan.has_bwd:
             out7 = _DarknetTrainFn.apply(self, plan, x, targets, *self._plist)
         else:
@@ -353,6 +393,10 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
         layout = lower.analyse(self.module_defs, self.module_list, cin, H, W)
         cx = lower.Lowering(plan, self, layout, xin, B, T, with_targets)          # (allocates the concat buffers)
         plan.call(plan.fwd, netplan._zero_tensor, plan.out7)
+        plan.cls_out = None
+        if with_targets and self.cls_loss != 0:
+            plan.cls_out = torch.zeros(1, dtype=torch.float32, device=device)
+            plan.call(plan.fwd, netplan._zero_tensor, plan.cls_out)
         if bn_train and plan.stats_xacc:                          # exact accumulators of the forward statistics (engine.fold_forward_xstats): one memset per forward
             plan._xacc_arena = torch.zeros(plan.stats_xacc_words, dtype=torch.int64, device=device)
             plan.keep.append(plan._xacc_arena)

@@ -112,7 +112,8 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
           checkpoint_interval, augment_affine, augment_hsv, lr_flip, ud_flip, momentum, gamma, lr, weight_decay, vis_batch, data_aug, blur,
           salt, noise, contrast, sharpen, ts, debug_mode, upload_dataset, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
           val_tolerance, min_epochs, log=print, device=None, precision=None, decode=None, num_workers=None, cache_bytes=None, state=None,
-          clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0, ema_warmup=10, mosaic=0.0, mosaic_off_epochs=0):
+          clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0, ema_warmup=10, mosaic=0.0, mosaic_off_epochs=0,
+          cls_loss=0.0, cls_mode="ce"):
     """train.py's `main` (train.py:95-259) with its keyword arguments, on the native pieces: `ImageLabelBatches` for both loaders (the
     reference's option mapping: the validation loader without augmentation, flips or shuffling; batch size 1 and no shuffle in
     `debug_mode`), `FusedAdam` / `FusedSGD`, `StepLR(step_size=1, gamma)` stepped at the top of every epoch as there, `run_epoch` above,
@@ -136,7 +137,10 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
     `mosaic` > 0 wraps the TRAINING loader in `MosaicBatches(p=mosaic)`: each training image is, with that probability,
     composed from four tiles of its batch on the device.  The validation loader never is.  The last `mosaic_off_epochs` epochs of
     `num_epochs` run on the loader's own batches.  One more line follows each training epoch, after the epoch's wait and from one read of the
-    wrapper's counters.  0 (the default): no wrapper is constructed, nothing changes."""
+    wrapper's counters.  0 (the default): no wrapper is constructed, nothing changes.
+
+    `cls_loss` != 0 is Darknet's: the class loss of the heads (`cls_mode` 'ce' or 'bce') joins the total that is logged and
+    minimised; the six logged parts keep their meaning.  0 (the default): nothing changes."""
     from .models import Darknet
     from .validate import validate
     from ..data.images import ImageLabelBatches
@@ -146,7 +150,7 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
 
     log("Initializing model")
     model = Darknet(config_path=model_cfg, xy_loss=xy_loss, wh_loss=wh_loss, no_object_loss=no_object_loss, object_loss=object_loss,
-                    vanilla_anchor=vanilla_anchor, precision=precision)
+                    vanilla_anchor=vanilla_anchor, precision=precision, cls_loss=cls_loss, cls_mode=cls_mode)
     img_width, img_height = model.img_size()
     bw = model.get_bw()
     validate_uri, train_uri = model.get_links()
@@ -311,6 +315,8 @@ def _parser():
     parser.add_argument('--ema_warmup', type=int, default=10, help='EMA warm-up: update t uses min(ema_decay, (1 + t) / (ema_warmup + t))')
     parser.add_argument('--mosaic', type=float, default=0.0, help='compose each training image from four tiles of its batch with this probability, on the device (0 = off)')
     parser.add_argument('--mosaic_off_epochs', type=int, default=0, help='train the last N of num_epochs epochs without mosaic')
+    parser.add_argument('--cls_loss', type=float, default=0.0, help='weight of the class loss of the heads, computed on the device (0 = off, as the reference hard-codes it)')
+    parser.add_argument('--cls_mode', type=str, default="ce", choices=("ce", "bce"), help='ce: cross entropy over the class sigmoids (the reference\'s statement); bce: independent logistic classifiers')
     return parser
 
 
@@ -326,7 +332,7 @@ def main(argv=None):
                  wh_loss=opt.wh_loss, no_object_loss=opt.no_object_loss, object_loss=opt.object_loss, vanilla_anchor=opt.vanilla_anchor,
                  val_tolerance=opt.val_tolerance, min_epochs=opt.min_epochs, clip_grad_norm=opt.clip_grad_norm,
                  skip_nonfinite=opt.skip_nonfinite, ema_decay=opt.ema_decay, ema_warmup=opt.ema_warmup, mosaic=opt.mosaic,
-                 mosaic_off_epochs=opt.mosaic_off_epochs)
+                 mosaic_off_epochs=opt.mosaic_off_epochs, cls_loss=opt.cls_loss, cls_mode=opt.cls_mode)
 
 
 if __name__ == '__main__':
