@@ -1,5 +1,6 @@
 """ctypes binding of libmdcv_hip.so, of libmdcv_aug.so and libmdcv_kptaug.so (device work outside the training step: `aug_lib()`,
-DESIGN §29; `kptaug_lib()`) and of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`).
+DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`) and of
+libmdcv_box.so (its opt-in box loss: `box_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -24,6 +25,10 @@ CLS_HEADER = os.path.join(ROOT, "include", "mdcv_cls.h")
 CLS_LIB_PATH = os.path.join(_HERE, "libmdcv_cls.so")
 CLS_MODES = {"ce": 0, "bce": 1}                  # include/mdcv_cls.h MDCV_CLS_CE / MDCV_CLS_BCE
 CLS_ERR_WORD = 3                                 # int32 index of the err word in a class workspace (MDCV_CLS_ERR_WORD)
+
+BOX_HEADER = os.path.join(ROOT, "include", "mdcv_box.h")
+BOX_LIB_PATH = os.path.join(_HERE, "libmdcv_box.so")
+BOX_MODES = {"giou": 0, "diou": 1, "ciou": 2}    # include/mdcv_box.h MDCV_BOX_GIOU / MDCV_BOX_DIOU / MDCV_BOX_CIOU
 
 F32, BF16 = 0, 1
 
@@ -136,6 +141,24 @@ def cls_mode(name):
     if name not in CLS_MODES:
         raise ValueError(f"cls_mode must be one of {sorted(CLS_MODES)}, got {name!r}")
     return CLS_MODES[name]
+
+
+_box = None
+
+
+def box_lib():
+    """libmdcv_box.so behind include/mdcv_box.h: the same binding and `check`, loaded on first use -- by a model built
+    with box_loss != 0 only"""
+    global _box
+    if _box is None:
+        _box = _Lib(BOX_LIB_PATH, BOX_HEADER, "libmdcv_box")
+    return _box
+
+
+def box_mode(name):
+    if name not in BOX_MODES:
+        raise ValueError(f"box_mode must be one of {sorted(BOX_MODES)}, got {name!r}")
+    return BOX_MODES[name]
 
 
 def require_gpu(t=None):

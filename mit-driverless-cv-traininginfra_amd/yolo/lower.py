@@ -389,7 +389,17 @@ def lower_yolo(cx, i, d):
         plan.call(plan.fwd, K.yolo_cls_loss, plan.dtype, lg.act.ptr, lg.act.ldc, plan.targets.data_ptr(), anchors.data_ptr(), *geo[:6], *cls,
                   ws.data_ptr(), cws.data_ptr(), plan.out7.data_ptr(), plan.cls_out.data_ptr())
         plan.watch_cls(cws)
-    return YoloHead(lg, anchors, ws, geo, cls)
+    box = None
+    if yl.box_loss != 0:                                     # opt-in box loss (csrc/yolo_box.hip): behind the head, same stream
+        K = _lib.box_lib()
+        box = (float(yl.ignore_thres), _lib.box_mode(yl.box_mode), float(yl.box_loss))
+        bws = torch.zeros(int(K.yolo_box_workspace_bytes()), dtype=torch.uint8, device=plan.device)
+        plan.keep.append(bws)
+        row = plan.box_out[plan.box_heads]                   # this head's (loss_box, mean IoU) pair
+        plan.box_heads += 1
+        plan.call(plan.fwd, K.yolo_box_loss, plan.dtype, lg.act.ptr, lg.act.ldc, plan.targets.data_ptr(), anchors.data_ptr(), *geo[:6], *box,
+                  ws.data_ptr(), bws.data_ptr(), plan.out7.data_ptr(), row.data_ptr())
+    return YoloHead(lg, anchors, ws, geo, cls, box)
 
 
 @dataclass
@@ -399,6 +409,7 @@ class YoloHead:
     ws: torch.Tensor            # head workspace (csrc/yolo_head.hip)
     geo: tuple
     cls: tuple = None           # (thresh, mode, cls_loss) of the class loss, or None: off
+    box: tuple = None           # (thresh, mode, box_loss) of the box loss, or None: off
 
     def backward(self, plan):
         lg = self.lg
@@ -409,6 +420,9 @@ class YoloHead:
         if self.cls is not None:                             # overwrites the class channels of the owned cells in the plane just written
             plan.call(plan.bwd, _lib.cls_lib().yolo_cls_grad, plan.dtype, lg.act.ptr, lg.act.ldc, out.ptr, out.ldc, out.C,
                       plan.targets.data_ptr(), self.anchors.data_ptr(), *self.geo[:6], *self.cls, self.ws.data_ptr(), plan.gscale.data_ptr())
+        if self.box is not None:                             # adds to the x/y/w/h channels of the owned cells: the MSE gradients stay
+            plan.call(plan.bwd, _lib.box_lib().yolo_box_grad, plan.dtype, lg.act.ptr, lg.act.ldc, out.ptr, out.ldc, out.C,
+                      plan.targets.data_ptr(), self.anchors.data_ptr(), *self.geo[:6], *self.box, self.ws.data_ptr(), plan.gscale.data_ptr())
 
 
 FORWARD = {"convolutional": lower_convolutional, "shortcut": lower_shortcut, "maxpool": lower_maxpool, "upsample": lower_upsample,

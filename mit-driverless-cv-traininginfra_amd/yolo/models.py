@@ -13,7 +13,8 @@ fp32 master parameters (OIHW) and BatchNorm buffers.  There is no CPU fallback.
 
 Extra (non-reference) knobs: `precision=` ctor kwarg or env MDCV_PRECISION in {"bf16" (default), "fp32"};
 env MDCV_GRAPH=1 replays the plan through hipGraphs; `cls_loss=` / `cls_mode=` ctor kwargs switch the class loss on (the reference multiplies
-it by a hard-coded 0, models.py:203-205; csrc/yolo_cls.hip), default 0 = off: nothing of it is built, loaded or launched.
+it by a hard-coded 0, models.py:203-205; csrc/yolo_cls.hip, DESIGN §31), default 0 = off: nothing of it is built, loaded or launched;
+`box_loss=` / `box_mode=` likewise add a GIoU / DIoU / CIoU box loss beside the four MSE terms (csrc/yolo_box.hip), default 0.
 """
 from __future__ import division
 
@@ -46,7 +47,8 @@ class EmptyLayer(nn.Module):
     """Placeholder module for 'route' and 'shortcut' sections (keeps module_list indices aligned with the cfg)."""
 
 
-def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, *, cls_loss=0.0, cls_mode="ce"):
+def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, *, cls_loss=0.0, cls_mode="ce",
+                   box_loss=0.0, box_mode="ciou"):
     """cfg sections -> (hyperparams, nn.ModuleList).  Naming / ordering rules follow reference models.py:15-110 so that
     state_dict keys and `.weights` traversal (`module[0]` conv, `module[1]` BN) stay compatible."""
     hyper = module_defs.pop(0)
@@ -96,7 +98,8 @@ def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, v
             seq.add_module("shortcut_%d" % i, EmptyLayer())
         elif kind == "yolo":
             seq.add_module("yolo_%d" % i, YOLOLayer([anchors_all[v] for v in masks[head]], n_cls, img_h, img_w, ignore, activation,
-                                                    xy_loss, wh_loss, object_loss, no_object_loss, cls_loss=cls_loss, cls_mode=cls_mode))
+                                                    xy_loss, wh_loss, object_loss, no_object_loss, cls_loss=cls_loss, cls_mode=cls_mode,
+                                                    box_loss=box_loss, box_mode=box_mode))
             head += 1
             filters = channels[-1]
         else:
@@ -140,13 +143,22 @@ class _YoloHeadFn(torch.autograd.Function):
                                     cws.data_ptr(), out7.data_ptr(), layer.loss_cls.data_ptr(), st), "yolo_cls_loss")
             if _CHECK_TARGETS and int(_cls_err_view(cws).item()):
                 raise IndexError(_BAD_CLASS_MSG)
-        ctx.saved = (lg, tg, anchors, ws, geo, cp, ch, cls)
+        box = None
+        if layer.box_loss != 0:                                   # so does the box loss
+            K = _lib.box_lib()
+            box = (float(layer.ignore_thres), _lib.box_mode(layer.box_mode), float(layer.box_loss))
+            bws = torch.zeros(int(K.yolo_box_workspace_bytes()), dtype=torch.uint8, device=dev)
+            box_out = torch.zeros(2, dtype=torch.float32, device=dev)
+            layer.loss_box, layer.box_iou = box_out[:1], box_out[1:]
+            K.check(K.yolo_box_loss(_lib.F32, lg.data_ptr(), cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], *box, ws.data_ptr(),
+                                    bws.data_ptr(), out7.data_ptr(), box_out.data_ptr(), st), "yolo_box_loss")
+        ctx.saved = (lg, tg, anchors, ws, geo, cp, ch, cls, box)
         return out7
 
     @staticmethod
     def backward(ctx, gout):
         L = _lib.lib()
-        lg, tg, anchors, ws, geo, cp, ch, cls = ctx.saved
+        lg, tg, anchors, ws, geo, cp, ch, cls, box = ctx.saved
         B, Gh, Gw = geo[0], geo[4], geo[5]
         st = torch.cuda.current_stream().cuda_stream
         g = gout.contiguous()
@@ -157,6 +169,10 @@ class _YoloHeadFn(torch.autograd.Function):
             K = _lib.cls_lib()
             K.check(K.yolo_cls_grad(_lib.F32, lg.data_ptr(), cp, dl.data_ptr(), cp, cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], *cls,
                                     ws.data_ptr(), g.data_ptr(), st), "yolo_cls_grad")
+        if box is not None:                                       # adds to the x/y/w/h channels of the owned cells: the MSE gradients stay
+            K = _lib.box_lib()
+            K.check(K.yolo_box_grad(_lib.F32, lg.data_ptr(), cp, dl.data_ptr(), cp, cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], *box,
+                                    ws.data_ptr(), g.data_ptr(), st), "yolo_box_grad")
         ds = torch.empty(B, ch, Gh, Gw, dtype=torch.float32, device=lg.device)
         L.check(L.nhwc_to_nchw(_lib.F32, dl.data_ptr(), cp, ds.data_ptr(), B, ch, Gh, Gw, st), "nhwc_to_nchw")
         return None, ds, None
@@ -166,14 +182,20 @@ class YOLOLayer(nn.Module):
     """Detection head.  ctor argument order as in the reference (note object_loss before no_object_loss, models.py:121).
     forward(sample, targets) -> (loss, tensor(6 parts: x,y,w,h,obj,noobj)) ; forward(sample) -> [B, A*G*G, 5+C].
     cls_loss != 0 adds the class loss (cls_mode 'ce': the reference's cross entropy over the class sigmoids; 'bce': independent logistic
-    classifiers) to `loss`; its value is `self.loss_cls` (a one-float device tensor) after a forward with targets."""
+    classifiers) to `loss`; its value is `self.loss_cls` (a one-float device tensor) after a forward with targets.
+    box_loss != 0 adds `box_loss * mean over owned cells of (1 - q)`, q the GIoU / DIoU / CIoU (box_mode) of the predicted and the labelled
+    box, beside the four MSE terms (set xy_loss = wh_loss = 0 to train on it alone); `self.loss_box` is its value and `self.box_iou` the
+    mean plain IoU of the owned cells, one-float device tensors."""
 
     def __init__(self, anchors, num_classes, img_height, img_width, build_targets_ignore_thresh, conv_activation, xy_loss, wh_loss,
-                 object_loss, no_object_loss, *, cls_loss=0.0, cls_mode="ce"):
+                 object_loss, no_object_loss, *, cls_loss=0.0, cls_mode="ce", box_loss=0.0, box_mode="ciou"):
         super().__init__()
         _lib.cls_mode(cls_mode)                                    # (ValueError for an unknown name, also when cls_loss == 0)
         self.cls_loss, self.cls_mode = float(cls_loss), cls_mode
         self.loss_cls = None
+        _lib.box_mode(box_mode)                                    # (the same for box_loss == 0)
+        self.box_loss, self.box_mode = float(box_loss), box_mode
+        self.loss_box = self.box_iou = None
         self.anchors = anchors
         self.num_anchors = len(anchors)
         self.num_classes = num_classes
@@ -296,13 +318,15 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
     """YOLOv3 object detection model (reference: CVC-YOLOv3/models.py:222-422)."""
 
     def __init__(self, config_path, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, precision=None, *, cls_loss=0.0,
-                 cls_mode="ce"):
+                 cls_mode="ce", box_loss=0.0, box_mode="ciou"):
         super().__init__()
         self.module_defs = parse_model_config(config_path)
         self.hyperparams, self.module_list = create_modules(self.module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
-                                                            cls_loss=cls_loss, cls_mode=cls_mode)
+                                                            cls_loss=cls_loss, cls_mode=cls_mode, box_loss=box_loss, box_mode=box_mode)
         self.cls_loss, self.cls_mode = float(cls_loss), cls_mode
         self.loss_cls = None             # after a forward with targets and cls_loss != 0: the class part of out[0], summed over the heads (device, 1 float)
+        self.box_loss, self.box_mode = float(box_loss), box_mode
+        self._box_out = None             # after a forward with targets and box_loss != 0: the plan's [heads, 2] (loss_box, mean IoU) rows
         h = self.hyperparams
         self.img_width, self.img_height = int(h["width"]), int(h["height"])
         self.onnx_height = int(h["onnx_height"])
@@ -335,6 +359,16 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
         out = super().load_state_dict(*args, **kw)
         self._params_changed()
         return out
+
+    @property
+    def loss_box(self):
+        """the box part of out[0] of the last forward with targets, summed over the heads (device, 1 float); None with box_loss == 0"""
+        return None if self._box_out is None else self._box_out[:, 0].sum(0, keepdim=True)
+
+    @property
+    def box_iou(self):
+        """mean over the heads of the mean plain IoU of their owned cells, formed on the device from the plan's rows (no host read)"""
+        return None if self._box_out is None else self._box_out[:, 1].mean(0, keepdim=True)
 
     # ---- getters consumed by train.py / validate.py / detect.py (reference models.py:279-310)
     def get_start_weight_dim(self): return self.start_weights_dim
@@ -371,6 +405,7 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
             plan.run_forward(x)
             return plan.eval_out.clone()
         self.loss_cls = plan.cls_out         # (the plan's own tensor: it holds this forward's value until the next forward through the plan)
+        self._box_out = plan.box_out
         if torch.is_grad_enabled() and plan.has_bwd:
             out7 = _DarknetTrainFn.apply(self, plan, x, targets, *self._plist)
         else:
@@ -397,6 +432,10 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
         if with_targets and self.cls_loss != 0:
             plan.cls_out = torch.zeros(1, dtype=torch.float32, device=device)
             plan.call(plan.fwd, netplan._zero_tensor, plan.cls_out)
+        plan.box_out, plan.box_heads = None, 0
+        if with_targets and self.box_loss != 0:               # one (loss_box, mean IoU) row per head, handed out by lower_yolo
+            plan.box_out = torch.zeros(sum(d["type"] == "yolo" for d in self.module_defs), 2, dtype=torch.float32, device=device)
+            plan.call(plan.fwd, netplan._zero_tensor, plan.box_out)
         if bn_train and plan.stats_xacc:                          # exact accumulators of the forward statistics (engine.fold_forward_xstats): one memset per forward
             plan._xacc_arena = torch.zeros(plan.stats_xacc_words, dtype=torch.int64, device=device)
             plan.keep.append(plan._xacc_arena)
