@@ -5,7 +5,8 @@ detect.py) binds the MI355X-native classes.  The directory holds this one module
 `from utils.nms import nms` and `import validate` (train.py:20-22) keep resolving to the reference's own files.
 
 `Darknet` keeps the reference's signature; behind it, keyword-only, `cls_loss=` / `cls_mode=` switch on the class loss the reference
-multiplies by 0, and `box_loss=` / `box_mode=` a GIoU / DIoU / CIoU box loss beside the four MSE terms.
+multiplies by 0, and `box_loss=` / `box_mode=` a GIoU / DIoU / CIoU box loss beside the four MSE terms,
+and `pred_ignore=` Darknet's prediction-IoU `ignore_thresh` for the no-object term.
 
 `use_hip_postprocessing()` optionally swaps the reference's per-image NMS loop for the batched HIP one, in whatever `utils.nms`
 module is importable (call it before `import validate`).

@@ -1,6 +1,7 @@
 """ctypes binding of libmdcv_hip.so, of libmdcv_aug.so and libmdcv_kptaug.so (device work outside the training step: `aug_lib()`,
-DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`) and of
-libmdcv_box.so (its opt-in box loss: `box_lib()`).
+DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`), of
+libmdcv_box.so (its opt-in box loss: `box_lib()`) and of libmdcv_ign.so (the opt-in prediction-IoU ignore rule of its
+no-object term: `ign_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -29,6 +30,9 @@ CLS_ERR_WORD = 3                                 # int32 index of the err word i
 BOX_HEADER = os.path.join(ROOT, "include", "mdcv_box.h")
 BOX_LIB_PATH = os.path.join(_HERE, "libmdcv_box.so")
 BOX_MODES = {"giou": 0, "diou": 1, "ciou": 2}    # include/mdcv_box.h MDCV_BOX_GIOU / MDCV_BOX_DIOU / MDCV_BOX_CIOU
+
+IGN_HEADER = os.path.join(ROOT, "include", "mdcv_ign.h")
+IGN_LIB_PATH = os.path.join(_HERE, "libmdcv_ign.so")
 
 F32, BF16 = 0, 1
 
@@ -159,6 +163,26 @@ def box_mode(name):
     if name not in BOX_MODES:
         raise ValueError(f"box_mode must be one of {sorted(BOX_MODES)}, got {name!r}")
     return BOX_MODES[name]
+
+
+_ign = None
+
+
+def ign_lib():
+    """libmdcv_ign.so behind include/mdcv_ign.h: the same binding and `check`, loaded on first use -- by a model built
+    with pred_ignore != 0 only"""
+    global _ign
+    if _ign is None:
+        _ign = _Lib(IGN_LIB_PATH, IGN_HEADER, "libmdcv_ign")
+    return _ign
+
+
+def pred_ignore(value):
+    """the threshold as a float: 0 is off, anything outside [0, 1) a ValueError (NaN included)"""
+    v = float(value)
+    if not 0.0 <= v < 1.0:
+        raise ValueError(f"pred_ignore must lie in [0, 1) (0 = off), got {value!r}")
+    return v
 
 
 def require_gpu(t=None):

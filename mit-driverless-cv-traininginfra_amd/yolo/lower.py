@@ -380,6 +380,15 @@ def lower_yolo(cx, i, d):
     plan.call(plan.fwd, L.yolo_head_train, plan.dtype, lg.act.ptr, lg.act.ldc, None, 0, lg.act.C, plan.targets.data_ptr(),
               anchors.data_ptr(), *geo, ws.data_ptr(), plan.out7.data_ptr(), None)
     plan.watch_head(ws, B, A, Gh, Gw)
+    ign = None
+    if yl.pred_ignore != 0:                                  # opt-in prediction-IoU ignore rule (csrc/yolo_ign.hip): directly
+        K = _lib.ign_lib()                                   # behind the head; reads logits / targets / ws, WRITES acc[5], acc[7] of ws
+        ign = torch.zeros(int(K.yolo_ign_workspace_bytes(B, A, Gh, Gw)), dtype=torch.uint8, device=plan.device)
+        plan.keep.append(ign)
+        row = plan.ign_out[plan.ign_heads]                   # this head's (n, nN') pair
+        plan.ign_heads += 1
+        plan.call(plan.fwd, K.yolo_ign_loss, plan.dtype, lg.act.ptr, lg.act.ldc, plan.targets.data_ptr(), anchors.data_ptr(), *geo[:6],
+                  float(yl.pred_ignore), float(yl.no_object_loss), ws.data_ptr(), ign.data_ptr(), plan.out7.data_ptr(), row.data_ptr())
     cls = None
     if yl.cls_loss != 0:                                     # opt-in class loss (csrc/yolo_cls.hip): behind the head, same stream
         K = _lib.cls_lib()
@@ -399,7 +408,7 @@ def lower_yolo(cx, i, d):
         plan.box_heads += 1
         plan.call(plan.fwd, K.yolo_box_loss, plan.dtype, lg.act.ptr, lg.act.ldc, plan.targets.data_ptr(), anchors.data_ptr(), *geo[:6], *box,
                   ws.data_ptr(), bws.data_ptr(), plan.out7.data_ptr(), row.data_ptr())
-    return YoloHead(lg, anchors, ws, geo, cls, box)
+    return YoloHead(lg, anchors, ws, geo, cls, box, ign)
 
 
 @dataclass
@@ -410,6 +419,7 @@ class YoloHead:
     geo: tuple
     cls: tuple = None           # (thresh, mode, cls_loss) of the class loss, or None: off
     box: tuple = None           # (thresh, mode, box_loss) of the box loss, or None: off
+    ign: torch.Tensor = None    # workspace of the prediction-IoU ignore rule (its mask of ignored cells), or None: off
 
     def backward(self, plan):
         lg = self.lg
@@ -417,6 +427,10 @@ class YoloHead:
         assert add is None
         plan.call(plan.bwd, plan.L.yolo_head_grad, plan.dtype, lg.act.ptr, lg.act.ldc, out.ptr, out.ldc, out.C, plan.targets.data_ptr(),
                   self.anchors.data_ptr(), *self.geo, self.ws.data_ptr(), plan.gscale.data_ptr())
+        if self.ign is not None:                             # reads its mask, writes the conf word of the ignored cells in the plane just written
+            B, _, A, C, Gh, Gw = self.geo[:6]
+            plan.call(plan.bwd, _lib.ign_lib().yolo_ign_grad, plan.dtype, out.ptr, out.ldc, out.C, B, A, C, Gh, Gw, self.ign.data_ptr(),
+                      plan.gscale.data_ptr())
         if self.cls is not None:                             # overwrites the class channels of the owned cells in the plane just written
             plan.call(plan.bwd, _lib.cls_lib().yolo_cls_grad, plan.dtype, lg.act.ptr, lg.act.ldc, out.ptr, out.ldc, out.C,
                       plan.targets.data_ptr(), self.anchors.data_ptr(), *self.geo[:6], *self.cls, self.ws.data_ptr(), plan.gscale.data_ptr())

@@ -14,7 +14,9 @@ fp32 master parameters (OIHW) and BatchNorm buffers.  There is no CPU fallback.
 Extra (non-reference) knobs: `precision=` ctor kwarg or env MDCV_PRECISION in {"bf16" (default), "fp32"};
 env MDCV_GRAPH=1 replays the plan through hipGraphs; `cls_loss=` / `cls_mode=` ctor kwargs switch the class loss on (the reference multiplies
 it by a hard-coded 0, models.py:203-205; csrc/yolo_cls.hip, DESIGN §31), default 0 = off: nothing of it is built, loaded or launched;
-`box_loss=` / `box_mode=` likewise add a GIoU / DIoU / CIoU box loss beside the four MSE terms (csrc/yolo_box.hip), default 0.
+`box_loss=` / `box_mode=` likewise add a GIoU / DIoU / CIoU box loss beside the four MSE terms (csrc/yolo_box.hip, DESIGN §32), default 0;
+`pred_ignore=` is Darknet's `ignore_thresh`: an unowned cell whose predicted box overlaps a label of its image by more than it leaves the
+no-object term (csrc/yolo_ign.hip), default 0 = off.
 """
 from __future__ import division
 
@@ -48,7 +50,7 @@ class EmptyLayer(nn.Module):
 
 
 def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, *, cls_loss=0.0, cls_mode="ce",
-                   box_loss=0.0, box_mode="ciou"):
+                   box_loss=0.0, box_mode="ciou", pred_ignore=0.0):
     """cfg sections -> (hyperparams, nn.ModuleList).  Naming / ordering rules follow reference models.py:15-110 so that
     state_dict keys and `.weights` traversal (`module[0]` conv, `module[1]` BN) stay compatible."""
     hyper = module_defs.pop(0)
@@ -99,7 +101,7 @@ def create_modules(module_defs, xy_loss, wh_loss, no_object_loss, object_loss, v
         elif kind == "yolo":
             seq.add_module("yolo_%d" % i, YOLOLayer([anchors_all[v] for v in masks[head]], n_cls, img_h, img_w, ignore, activation,
                                                     xy_loss, wh_loss, object_loss, no_object_loss, cls_loss=cls_loss, cls_mode=cls_mode,
-                                                    box_loss=box_loss, box_mode=box_mode))
+                                                    box_loss=box_loss, box_mode=box_mode, pred_ignore=pred_ignore))
             head += 1
             filters = channels[-1]
         else:
@@ -133,6 +135,14 @@ class _YoloHeadFn(torch.autograd.Function):
                                   out7.data_ptr(), None, st), "yolo_head_train")
         if _CHECK_TARGETS and int(_head_err_view(ws, B, A, Gh, Gw).item()):
             raise IndexError(_BAD_TARGET_MSG)
+        ign = None
+        if layer.pred_ignore != 0:                                # the prediction-IoU ignore rule directly behind the head:
+            K = _lib.ign_lib()                                    # it rewrites acc[5] / acc[7] of `ws`, which the head's gradient reads
+            ign = torch.zeros(int(K.yolo_ign_workspace_bytes(B, A, Gh, Gw)), dtype=torch.uint8, device=dev)
+            layer.noobj_ignored = torch.zeros(2, dtype=torch.float32, device=dev)
+            K.check(K.yolo_ign_loss(_lib.F32, lg.data_ptr(), cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], float(layer.pred_ignore),
+                                    float(layer.no_object_loss), ws.data_ptr(), ign.data_ptr(), out7.data_ptr(),
+                                    layer.noobj_ignored.data_ptr(), st), "yolo_ign_loss")
         cls = None
         if layer.cls_loss != 0:                                   # the class loss rides behind the head, on the same stream
             K = _lib.cls_lib()
@@ -152,19 +162,22 @@ class _YoloHeadFn(torch.autograd.Function):
             layer.loss_box, layer.box_iou = box_out[:1], box_out[1:]
             K.check(K.yolo_box_loss(_lib.F32, lg.data_ptr(), cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], *box, ws.data_ptr(),
                                     bws.data_ptr(), out7.data_ptr(), box_out.data_ptr(), st), "yolo_box_loss")
-        ctx.saved = (lg, tg, anchors, ws, geo, cp, ch, cls, box)
+        ctx.saved = (lg, tg, anchors, ws, geo, cp, ch, cls, box, ign)
         return out7
 
     @staticmethod
     def backward(ctx, gout):
         L = _lib.lib()
-        lg, tg, anchors, ws, geo, cp, ch, cls, box = ctx.saved
+        lg, tg, anchors, ws, geo, cp, ch, cls, box, ign = ctx.saved
         B, Gh, Gw = geo[0], geo[4], geo[5]
         st = torch.cuda.current_stream().cuda_stream
         g = gout.contiguous()
         dl = torch.empty_like(lg)
         L.check(L.yolo_head_grad(_lib.F32, lg.data_ptr(), cp, dl.data_ptr(), cp, cp, tg.data_ptr(), anchors.data_ptr(), *geo, ws.data_ptr(),
                                  g.data_ptr(), st), "yolo_head_grad")
+        if ign is not None:                                       # the conf word of the ignored cells
+            K = _lib.ign_lib()
+            K.check(K.yolo_ign_grad(_lib.F32, dl.data_ptr(), cp, cp, B, geo[2], geo[3], Gh, Gw, ign.data_ptr(), g.data_ptr(), st), "yolo_ign_grad")
         if cls is not None:
             K = _lib.cls_lib()
             K.check(K.yolo_cls_grad(_lib.F32, lg.data_ptr(), cp, dl.data_ptr(), cp, cp, tg.data_ptr(), anchors.data_ptr(), *geo[:6], *cls,
@@ -185,11 +198,15 @@ class YOLOLayer(nn.Module):
     classifiers) to `loss`; its value is `self.loss_cls` (a one-float device tensor) after a forward with targets.
     box_loss != 0 adds `box_loss * mean over owned cells of (1 - q)`, q the GIoU / DIoU / CIoU (box_mode) of the predicted and the labelled
     box, beside the four MSE terms (set xy_loss = wh_loss = 0 to train on it alone); `self.loss_box` is its value and `self.box_iou` the
-    mean plain IoU of the owned cells, one-float device tensors."""
+    mean plain IoU of the owned cells, one-float device tensors.
+    pred_ignore in (0, 1) is Darknet's `ignore_thresh`: an unowned cell whose predicted box overlaps a label of its own image by more than
+    it leaves the no-object term, value and gradient; `self.noobj_ignored` is (n ignored cells, nN' negatives left), a two-float device tensor."""
 
     def __init__(self, anchors, num_classes, img_height, img_width, build_targets_ignore_thresh, conv_activation, xy_loss, wh_loss,
-                 object_loss, no_object_loss, *, cls_loss=0.0, cls_mode="ce", box_loss=0.0, box_mode="ciou"):
+                 object_loss, no_object_loss, *, cls_loss=0.0, cls_mode="ce", box_loss=0.0, box_mode="ciou", pred_ignore=0.0):
         super().__init__()
+        self.pred_ignore = _lib.pred_ignore(pred_ignore)           # (ValueError outside [0, 1))
+        self.noobj_ignored = None
         _lib.cls_mode(cls_mode)                                    # (ValueError for an unknown name, also when cls_loss == 0)
         self.cls_loss, self.cls_mode = float(cls_loss), cls_mode
         self.loss_cls = None
@@ -318,15 +335,18 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
     """YOLOv3 object detection model (reference: CVC-YOLOv3/models.py:222-422)."""
 
     def __init__(self, config_path, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor, precision=None, *, cls_loss=0.0,
-                 cls_mode="ce", box_loss=0.0, box_mode="ciou"):
+                 cls_mode="ce", box_loss=0.0, box_mode="ciou", pred_ignore=0.0):
         super().__init__()
         self.module_defs = parse_model_config(config_path)
         self.hyperparams, self.module_list = create_modules(self.module_defs, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
-                                                            cls_loss=cls_loss, cls_mode=cls_mode, box_loss=box_loss, box_mode=box_mode)
+                                                            cls_loss=cls_loss, cls_mode=cls_mode, box_loss=box_loss, box_mode=box_mode,
+                                                            pred_ignore=pred_ignore)
         self.cls_loss, self.cls_mode = float(cls_loss), cls_mode
         self.loss_cls = None             # after a forward with targets and cls_loss != 0: the class part of out[0], summed over the heads (device, 1 float)
         self.box_loss, self.box_mode = float(box_loss), box_mode
         self._box_out = None             # after a forward with targets and box_loss != 0: the plan's [heads, 2] (loss_box, mean IoU) rows
+        self.pred_ignore = _lib.pred_ignore(pred_ignore)
+        self.noobj_ignored = None        # after a forward with targets and pred_ignore != 0: [heads, 2] rows (n ignored, nN' left), on the device
         h = self.hyperparams
         self.img_width, self.img_height = int(h["width"]), int(h["height"])
         self.onnx_height = int(h["onnx_height"])
@@ -406,6 +426,7 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
             return plan.eval_out.clone()
         self.loss_cls = plan.cls_out         # (the plan's own tensor: it holds this forward's value until the next forward through the plan)
         self._box_out = plan.box_out
+        self.noobj_ignored = plan.ign_out
         if torch.is_grad_enabled() and plan.has_bwd:
             out7 = _DarknetTrainFn.apply(self, plan, x, targets, *self._plist)
         else:
@@ -436,6 +457,9 @@ class Darknet(netplan.FlatParamsMixin, nn.Module):
         if with_targets and self.box_loss != 0:               # one (loss_box, mean IoU) row per head, handed out by lower_yolo
             plan.box_out = torch.zeros(sum(d["type"] == "yolo" for d in self.module_defs), 2, dtype=torch.float32, device=device)
             plan.call(plan.fwd, netplan._zero_tensor, plan.box_out)
+        plan.ign_out, plan.ign_heads = None, 0
+        if with_targets and self.pred_ignore != 0:            # one (n, nN') row per head, handed out by lower_yolo and written whole each forward
+            plan.ign_out = torch.zeros(sum(d["type"] == "yolo" for d in self.module_defs), 2, dtype=torch.float32, device=device)
         if bn_train and plan.stats_xacc:                          # exact accumulators of the forward statistics (engine.fold_forward_xstats): one memset per forward
             plan._xacc_arena = torch.zeros(plan.stats_xacc_words, dtype=torch.int64, device=device)
             plan.keep.append(plan._xacc_arena)

@@ -113,7 +113,7 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
           salt, noise, contrast, sharpen, ts, debug_mode, upload_dataset, xy_loss, wh_loss, no_object_loss, object_loss, vanilla_anchor,
           val_tolerance, min_epochs, log=print, device=None, precision=None, decode=None, num_workers=None, cache_bytes=None, state=None,
           clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0, ema_warmup=10, mosaic=0.0, mosaic_off_epochs=0,
-          cls_loss=0.0, cls_mode="ce", box_loss=0.0, box_mode="ciou"):
+          cls_loss=0.0, cls_mode="ce", box_loss=0.0, box_mode="ciou", pred_ignore=0.0):
     """train.py's `main` (train.py:95-259) with its keyword arguments, on the native pieces: `ImageLabelBatches` for both loaders (the
     reference's option mapping: the validation loader without augmentation, flips or shuffling; batch size 1 and no shuffle in
     `debug_mode`), `FusedAdam` / `FusedSGD`, `StepLR(step_size=1, gamma)` stepped at the top of every epoch as there, `run_epoch` above,
@@ -144,7 +144,11 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
 
     `box_loss` != 0 is Darknet's too: `box_loss * mean(1 - q)` over the owned cells of every head, q the GIoU / DIoU / CIoU (`box_mode`) of
     the predicted and the labelled box, joins the total in the same way, beside the four MSE terms that `xy_loss` / `wh_loss`
-    weigh (0 there trains the box on it alone); `model.box_iou` is the mean IoU of the step, on the device.  0 (the default): nothing changes."""
+    weigh (0 there trains the box on it alone); `model.box_iou` is the mean IoU of the step, on the device.  0 (the default): nothing changes.
+
+    `pred_ignore` in (0, 1) is Darknet's as well: its `ignore_thresh` -- a cell nobody owns whose predicted box overlaps a label of its own
+    image by more than it leaves the no-object term; `model.noobj_ignored` counts such cells per head, on the device.  0 (the
+    default): nothing changes."""
     from .models import Darknet
     from .validate import validate
     from ..data.images import ImageLabelBatches
@@ -155,7 +159,7 @@ def train(*, evaluate, batch_size, optimizer_pick, model_cfg, weights_path, outp
     log("Initializing model")
     model = Darknet(config_path=model_cfg, xy_loss=xy_loss, wh_loss=wh_loss, no_object_loss=no_object_loss, object_loss=object_loss,
                     vanilla_anchor=vanilla_anchor, precision=precision, cls_loss=cls_loss, cls_mode=cls_mode, box_loss=box_loss,
-                    box_mode=box_mode)
+                    box_mode=box_mode, pred_ignore=pred_ignore)
     img_width, img_height = model.img_size()
     bw = model.get_bw()
     validate_uri, train_uri = model.get_links()
@@ -324,6 +328,7 @@ def _parser():
     parser.add_argument('--cls_mode', type=str, default="ce", choices=("ce", "bce"), help='ce: cross entropy over the class sigmoids (the reference\'s statement); bce: independent logistic classifiers')
     parser.add_argument('--box_loss', type=float, default=0.0, help='weight of the IoU-family box loss of the heads, computed on the device beside the four MSE terms (0 = off)')
     parser.add_argument('--box_mode', type=str, default="ciou", choices=("giou", "diou", "ciou"), help='which IoU variant the box loss takes: generalised, distance or complete IoU')
+    parser.add_argument('--pred_ignore', type=float, default=0.0, help="Darknet's ignore_thresh: an unowned cell whose predicted box has an IoU above this with a label of its image leaves the no-object loss (0 = off)")
     return parser
 
 
@@ -340,7 +345,7 @@ def main(argv=None):
                  val_tolerance=opt.val_tolerance, min_epochs=opt.min_epochs, clip_grad_norm=opt.clip_grad_norm,
                  skip_nonfinite=opt.skip_nonfinite, ema_decay=opt.ema_decay, ema_warmup=opt.ema_warmup, mosaic=opt.mosaic,
                  mosaic_off_epochs=opt.mosaic_off_epochs, cls_loss=opt.cls_loss, cls_mode=opt.cls_mode, box_loss=opt.box_loss,
-                 box_mode=opt.box_mode)
+                 box_mode=opt.box_mode, pred_ignore=opt.pred_ignore)
 
 
 if __name__ == '__main__':
