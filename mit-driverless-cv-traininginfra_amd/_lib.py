@@ -1,7 +1,8 @@
 """ctypes binding of libmdcv_hip.so, of libmdcv_aug.so and libmdcv_kptaug.so (device work outside the training step: `aug_lib()`,
 DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`), of
-libmdcv_box.so (its opt-in box loss: `box_lib()`) and of libmdcv_ign.so (the opt-in prediction-IoU ignore rule of its
-no-object term: `ign_lib()`).
+libmdcv_box.so (its opt-in box loss: `box_lib()`), of libmdcv_ign.so (the opt-in prediction-IoU ignore rule of its
+no-object term: `ign_lib()`) and of libmdcv_mcdet.so (the opt-in class-aware detection post-processing: `mcdet_lib()`,
+DESIGN §34).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -33,6 +34,10 @@ BOX_MODES = {"giou": 0, "diou": 1, "ciou": 2}    # include/mdcv_box.h MDCV_BOX_G
 
 IGN_HEADER = os.path.join(ROOT, "include", "mdcv_ign.h")
 IGN_LIB_PATH = os.path.join(_HERE, "libmdcv_ign.so")
+
+MCDET_HEADER = os.path.join(ROOT, "include", "mdcv_mcdet.h")
+MCDET_LIB_PATH = os.path.join(_HERE, "libmdcv_mcdet.so")
+MCDET_MAX_CLASSES = 65535                        # include/mdcv_mcdet.h MDCV_MCDET_MAX_CLASSES
 
 F32, BF16 = 0, 1
 
@@ -175,6 +180,18 @@ def ign_lib():
     if _ign is None:
         _ign = _Lib(IGN_LIB_PATH, IGN_HEADER, "libmdcv_ign")
     return _ign
+
+
+_mcdet = None
+
+
+def mcdet_lib():
+    """libmdcv_mcdet.so behind include/mdcv_mcdet.h: the same binding and `check`, loaded on first use -- by a
+    class_aware=True post-processing call or an nms(..., classes=) only"""
+    global _mcdet
+    if _mcdet is None:
+        _mcdet = _Lib(MCDET_LIB_PATH, MCDET_HEADER, "libmdcv_mcdet")
+    return _mcdet
 
 
 def pred_ignore(value):

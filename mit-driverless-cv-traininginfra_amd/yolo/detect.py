@@ -114,6 +114,9 @@ class BatchPlan:
             host[self.pool_off + off:self.pool_off + off + 3 * w * h] = f.reshape(-1)
 
 
+TILED_CLASS_AWARE = ("{}: class_aware=True is not available with tiles: the cross-tile merge (mdcv_detect_merge_tiles) is class-agnostic "
+                     "and would suppress overlapping boxes of different classes again; a class-aware tile merge is a later change")
+
 TILE_DESC = 4                            # MDCV_TILE_DESC
 MAX_TILES_PER_FRAME = 64                 # MDCV_TILE_MAX_PER_FRAME
 
@@ -210,13 +213,16 @@ class FrameDetector:
     """`FrameDetector(model).detect_frames(frames)`: see the module docstring.  conf_thres / nms_thres default to `model.get_threshs()`;
     at most `max_boxes` (<= top_k) boxes per frame are mapped and drawn, the most confident ones; `outline` is the one RGB triple of a
     call (default `ImageColor.getrgb("red")`).  Subclasses override `_plan` (the batch's layout), `_batch_boxes` (the boxes of a batch) and
-    `_result_type`; FrameConeDetector also `_annotate` and `_extras`; everything else -- staging, the copy back, the final synchronisation -- is shared."""
+    `_result_type`; FrameConeDetector also `_annotate` and `_extras`; everything else -- staging, the copy back, the final synchronisation -- is shared.
+    class_aware=True: `detect_postprocess(class_aware=True)` -- class scores, per-class NMS, `prob` the class score."""
 
     _result_type = FrameDetections
 
-    def __init__(self, model, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16):
+    def __init__(self, model, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
+                 class_aware=False):
         conf, nms, _ = model.get_threshs()
         self.model = model
+        self.class_aware = bool(class_aware)
         self.conf_thres = float(conf if conf_thres is None else conf_thres)
         self.nms_thres = float(nms if nms_thres is None else nms_thres)
         self.top_k, self.max_boxes, self.batch_size = int(top_k), int(max_boxes), int(batch_size)
@@ -252,7 +258,8 @@ class FrameDetector:
     def _batch_boxes(self, plan, dbuf, host, pool, st):
         imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
         self.model.eval()
-        det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k)
+        det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k,
+                                 class_aware=self.class_aware)
         count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
         return det.boxes, det.prob, count, None
 
@@ -411,8 +418,8 @@ class FrameConeDetector(FrameDetector):
     `detect_frames(..., return_crops=True)` also copies the crops back (a third synchronisation; tests and debugging)."""
 
     def __init__(self, model, keypoint_net, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 max_cones=64, bucket=64, colours=KPT_COLOURS_RGB):
-        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size)
+                 max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, class_aware=False):
+        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, class_aware)
         self.keypoint_net = keypoint_net
         self.max_cones, self.bucket = int(max_cones), int(bucket)
         if self.max_cones < 1 or self.bucket < 1:
@@ -494,7 +501,9 @@ class _Tiled:
     per frame.  Per batch, on the detector's one stream: all tiles resized from the pool in one launch, the eval forward and
     `detect_postprocess` in chunks of `tile_batch` tiles, ONE merge launch -- no count is read by the host."""
 
-    def _init_tiles(self, scale, tile_batch, contain_thres):
+    def _init_tiles(self, scale, tile_batch, contain_thres, class_aware=False):
+        if class_aware:
+            raise ValueError(TILED_CLASS_AWARE.format(type(self).__name__))
         if not callable(scale):
             value = float(scale)
             scale = lambda w, h: value                                       # noqa: E731
@@ -544,9 +553,9 @@ class TiledFrameDetector(_Tiled, FrameDetector):
     _result_type = TiledFrameDetections
 
     def __init__(self, model, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 tile_batch=32, contain_thres=None):
+                 tile_batch=32, contain_thres=None, class_aware=False):
         super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size)
-        self._init_tiles(scale, tile_batch, contain_thres)
+        self._init_tiles(scale, tile_batch, contain_thres, class_aware)
 
     def _plan(self, sizes, first):
         return TiledBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), first)
@@ -559,9 +568,9 @@ class TiledFrameConeDetector(_Tiled, FrameConeDetector):
     _result_type = TiledFrameCones
 
     def __init__(self, model, keypoint_net, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0),
-                 batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None):
+                 batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None, class_aware=False):
         super().__init__(model, keypoint_net, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, max_cones, bucket, colours)
-        self._init_tiles(scale, tile_batch, contain_thres)
+        self._init_tiles(scale, tile_batch, contain_thres, class_aware)
 
     def _plan(self, sizes, first):
         return TiledConeBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), self.max_cones, first)
@@ -598,30 +607,37 @@ def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, cont
     return FrameDetector(model, conf_thres=conf_thres, nms_thres=nms_thres, **kw)
 
 
-def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres, *, tiles=False, scale=1.0, contain_thres=None):
+def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres, *, tiles=False, scale=1.0, contain_thres=None,
+                      class_aware=False):
     """detect.py:60-111 for one RGB image file: mode 'image' saves under `output_path` with the file's own name, any other mode saves over
     `target_path` (the reference's rule for its dumped video frames); the saved path is returned.  With no detection the image is
     saved unannotated.  `device` must be the GPU the model is on (or None).  Each call builds its own detector: for many files use `detect`
     on their directory.  Keyword-only `tiles=True`: tile-and-scale inference at `scale` (TiledFrameDetector), the counterpart of training
-    with ts=True; the defaults are the reference's whole-frame pad and resize."""
+    with ts=True; the defaults are the reference's whole-frame pad and resize.  `class_aware`: FrameDetector's (not with tiles)."""
+    if tiles and class_aware:
+        raise ValueError(TILED_CLASS_AWARE.format("single_img_detect(tiles=True)"))
     frame = _open_rgb(target_path)
-    res = next(iter(_detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=1).detect_frames([frame])))
+    det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=1, class_aware=class_aware)
+    res = next(iter(det.detect_frames([frame])))
     if mode == "image":
         return _save(res.annotated, os.path.join(output_path, target_path.split("/")[-1]))
     return _save(res.annotated, target_path)
 
 
-def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16, *, tiles=False, scale=1.0, contain_thres=None):
+def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16, *, tiles=False, scale=1.0, contain_thres=None,
+           class_aware=False):
     """detect.py:113-196.  An image file (.jpg / .jpeg / .png / .tif) goes through `single_img_detect`; a directory has its image files,
     sorted by name, detected in batches of `batch_size` and written to `output_path` under their own names (-> the list of paths).
     Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead.
-    Keyword-only `tiles`, `scale`, `contain_thres`: as in `single_img_detect`."""
+    Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`: as in `single_img_detect`."""
+    if tiles and class_aware:
+        raise ValueError(TILED_CLASS_AWARE.format("detect(tiles=True)"))
     ext = os.path.splitext(target_path)[-1].lower()
     if os.path.isdir(target_path):
         names = sorted(f for f in os.listdir(target_path)
                        if os.path.splitext(f)[-1].lower() in IMG_FORMATS and os.path.isfile(os.path.join(target_path, f)))
         print(f"Detection Mode is: directory ({len(names)} images)")
-        det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=batch_size)
+        det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=batch_size, class_aware=class_aware)
         frames = (_open_rgb(os.path.join(target_path, f)) for f in names)
         paths = [_save(res.annotated, os.path.join(output_path, f)) for f, res in zip(names, det.detect_frames(frames))]
         print(f"Please check output images at {output_path}")
@@ -634,6 +650,7 @@ def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch
         raise ValueError(f"{target_path}: not an image file ({', '.join(IMG_FORMATS)}) or a directory")
     print("Detection Mode is: image")
     path = single_img_detect(target_path=target_path, output_path=output_path, mode="image", model=model, device=device,
-                             conf_thres=conf_thres, nms_thres=nms_thres, tiles=tiles, scale=scale, contain_thres=contain_thres)
+                             conf_thres=conf_thres, nms_thres=nms_thres, tiles=tiles, scale=scale, contain_thres=contain_thres,
+                             class_aware=class_aware)
     print(f"Please check output image at {path}")
     return path

@@ -246,10 +246,10 @@ class DatasetAP:
 
 
 def evaluate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=False, top_k=200, iou_thresholds=COCO_IOU_THRESHOLDS,
-             area_ranges=((0.0, math.inf), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, math.inf))):
+             area_ranges=((0.0, math.inf), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, math.inf)), class_aware=False):
     """`validate`'s loop with a `DatasetAP` beside the per-image statistics: one more launch per batch, nothing more read per batch.
     -> ((mean_mAP, mean_R, mean_P, seconds_per_image) exactly as `validate` returns them, APResult).  Prints validate's line, then one
-    line of AP@[.5:.95], AP50 and AP50 per area range (box areas in network-input px^2)."""
+    line of AP@[.5:.95], AP50 and AP50 per area range (box areas in network-input px^2).  class_aware: `detect_postprocess`'s keyword."""
     with torch.no_grad():
         t_start = time.time()
         conf_thres, nms_thres, iou_thres = model.get_threshs()
@@ -262,7 +262,7 @@ def evaluate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=F
         for _uris, imgs, targets in dataloader:
             imgs = imgs.to(device, non_blocking=True)
             targets = targets.to(device, non_blocking=True)
-            det = detect_postprocess(model(imgs), targets, conf_thres, nms_thres, iou_thres, width, height, top_k)
+            det = detect_postprocess(model(imgs), targets, conf_thres, nms_thres, iou_thres, width, height, top_k, class_aware=class_aware)
             stats.append(det.stats)
             acc.add(det, targets, width, height)
         if stats:
@@ -281,9 +281,14 @@ def evaluate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=F
         return (mean_mAP, mean_R, mean_P, dt / (n_images + 1e-12)), res
 
 
-def evaluate_frames(frames, labels, detector, scale=None, area_ranges=((0.0, math.inf),), iou_thresholds=COCO_IOU_THRESHOLDS, batch=64):
+def evaluate_frames(frames, labels, detector, scale=None, area_ranges=((0.0, math.inf),), iou_thresholds=COCO_IOU_THRESHOLDS, batch=64,
+                    class_aware=None):
     """whole frames through a `FrameDetector` / `TiledFrameDetector` against per-frame corner boxes in frame pixels -> APResult.
-    scale: the tiled detector's constant scale (its boxes are in scaled-frame pixels, so the labels are multiplied by it)."""
+    scale: the tiled detector's constant scale (its boxes are in scaled-frame pixels, so the labels are multiplied by it).
+    class_aware: None leaves the detector as it was built; True / False must agree with the detector's own `class_aware` (the labels
+    carry no class, so every box is scored as class 0 either way: what changes is which boxes the detector keeps)."""
+    if class_aware is not None and bool(class_aware) != bool(getattr(detector, "class_aware", False)):
+        raise ValueError(f"evaluate_frames: class_aware={class_aware!r} but the detector was built with class_aware={getattr(detector, 'class_aware', False)!r}")
     labels = list(labels)
     acc = DatasetAP(1, max(len(labels), 1), top_k=detector.top_k, iou_thresholds=iou_thresholds, area_ranges=area_ranges, device=detector.device)
     pending = []
@@ -315,6 +320,7 @@ def main(argv=None):
     p.add_argument('--conf_thres', type=float, default=None, help='frame mode: confidence threshold (default: the cfg\'s)')
     p.add_argument('--nms_thres', type=float, default=None, help='frame mode: NMS threshold (default: the cfg\'s)')
     p.add_argument('--precision', type=str, default=None, choices=["bf16", "fp32"], help='precision of the network (default: the model\'s)')
+    p.add_argument('--class_aware', action='store_true', help='class scores, per-class NMS and class-restricted matching (not with --tiles)')
     a = p.parse_args(argv)
     device = torch.device("cuda", torch.cuda.current_device())
     model = Darknet(config_path=a.model_cfg, xy_loss=2, wh_loss=1.6, no_object_loss=25, object_loss=0.1, vanilla_anchor=False, precision=a.precision)
@@ -327,14 +333,14 @@ def main(argv=None):
         width, height = model.img_size()
         loader = ImageLabelBatches(model.get_links()[0], a.dataset_path, width, height, num_images=model.num_images()[0], bw=model.get_bw(),
                                    ts=a.ts, batch_size=a.batch_size, shuffle=False, device=device)
-        return evaluate(dataloader=loader, model=model, device=device)[1]
+        return evaluate(dataloader=loader, model=model, device=device, class_aware=a.class_aware)[1]
     from ..data.images.labels import read_label_csv
     from .detect import _detector, _open_rgb
     rows = read_label_csv(a.labels, a.frames)
     labels = [np.stack([b[:, 0], b[:, 1], b[:, 0] + b[:, 3], b[:, 1] + b[:, 2]], axis=1).astype(np.float64) for *_x, b in rows]   # (x, y, h, w)
-    det = _detector(model, device, a.conf_thres, a.nms_thres, a.tiles, a.scale, a.contain_thres, batch_size=a.batch_size)
+    det = _detector(model, device, a.conf_thres, a.nms_thres, a.tiles, a.scale, a.contain_thres, batch_size=a.batch_size, class_aware=a.class_aware)
     frames = (_open_rgb(os.path.join(a.frames, os.path.basename(r[0]))) for r in rows)
-    res = evaluate_frames(frames, labels, det, scale=a.scale if a.tiles else None,
+    res = evaluate_frames(frames, labels, det, scale=a.scale if a.tiles else None, class_aware=a.class_aware,
                           area_ranges=((0.0, math.inf), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, math.inf)))
     print(res.summary())
     return res
