@@ -1,8 +1,8 @@
 """ctypes binding of libmdcv_hip.so, of libmdcv_aug.so and libmdcv_kptaug.so (device work outside the training step: `aug_lib()`,
 DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`), of
 libmdcv_box.so (its opt-in box loss: `box_lib()`), of libmdcv_ign.so (the opt-in prediction-IoU ignore rule of its
-no-object term: `ign_lib()`) and of libmdcv_mcdet.so (the opt-in class-aware detection post-processing: `mcdet_lib()`,
-DESIGN §34).
+no-object term: `ign_lib()`), of libmdcv_mcdet.so (the opt-in class-aware detection post-processing: `mcdet_lib()`,
+DESIGN §34) and of libmdcv_mctiles.so (the opt-in class-aware cross-tile merge: `mctiles_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -38,6 +38,10 @@ IGN_LIB_PATH = os.path.join(_HERE, "libmdcv_ign.so")
 MCDET_HEADER = os.path.join(ROOT, "include", "mdcv_mcdet.h")
 MCDET_LIB_PATH = os.path.join(_HERE, "libmdcv_mcdet.so")
 MCDET_MAX_CLASSES = 65535                        # include/mdcv_mcdet.h MDCV_MCDET_MAX_CLASSES
+
+MCTILES_HEADER = os.path.join(ROOT, "include", "mdcv_mctiles.h")
+MCTILES_LIB_PATH = os.path.join(_HERE, "libmdcv_mctiles.so")
+TILE_MERGES = ("agnostic", "per_class")          # the cross-tile merge of the tiled detectors: mdcv_detect_merge_tiles / _mc
 
 F32, BF16 = 0, 1
 
@@ -192,6 +196,18 @@ def mcdet_lib():
     if _mcdet is None:
         _mcdet = _Lib(MCDET_LIB_PATH, MCDET_HEADER, "libmdcv_mcdet")
     return _mcdet
+
+
+_mctiles = None
+
+
+def mctiles_lib():
+    """libmdcv_mctiles.so behind include/mdcv_mctiles.h: the same binding and `check`, loaded on first use -- by a tiled
+    detector built with class_aware=True, tile_merge="per_class" only"""
+    global _mctiles
+    if _mctiles is None:
+        _mctiles = _Lib(MCTILES_LIB_PATH, MCTILES_HEADER, "libmdcv_mctiles")
+    return _mctiles
 
 
 def pred_ignore(value):

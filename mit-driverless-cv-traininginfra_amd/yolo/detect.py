@@ -21,7 +21,8 @@ worker thread) while the device works on batch n.
 outlines and key-point discs drawn on the device).
 
 `TiledFrameDetector` / `TiledFrameConeDetector` run the same interface on the tiles training sees (`ts=True`): every tile at its native
-scale through the network, the tiles' detections merged per frame by `mdcv_detect_merge_tiles` (csrc/detect_tiles.hip).
+scale through the network, the tiles' detections merged per frame by `mdcv_detect_merge_tiles` (csrc/detect_tiles.hip) or,
+for a class-aware detector with `tile_merge="per_class"`, class by class by `mdcv_detect_merge_tiles_mc` (csrc/detect_tiles_mc.hip; §35).
 
 `single_img_detect` and `detect` take the reference's argument lists, so a caller swaps the import.  Departures, all
 documented in DESIGN.md §19: a box Pillow would refuse (x1 < x0, y1 < y0) or C could not convert (NaN, inf, magnitude >= 2^30) is skipped
@@ -72,11 +73,13 @@ class BatchPlan:
     """Byte layout of one batch.  Device buffer: [resize descriptors, tables and frame references (images.pack_layout)] [detect
     descriptors] [pool: the whole frames] [frame_boxes B,K,4 f64] [rects B,K,4 i32] [prob B,K f32] [count B i32] [skipped B i32];
     the pinned input is everything up to the end of the pool, the copy back is everything from the pool (or from the tables) on.
-    Subclasses choose the resize samples (`_samples`) and may put input tables behind the detect descriptors (`_tables`)."""
+    Subclasses choose the resize samples (`_samples`) and may put input tables behind the detect descriptors (`_tables`).
+    class_aware: [cls B,K i32] behind `skipped`; without it no byte of the layout moves."""
 
     src_off = None                           # tiled plans: [src B,K,2 i32] behind the tables
+    cls_off = None                           # class-aware plans: [cls B,K i32]
 
-    def __init__(self, sizes, width, height, K):
+    def __init__(self, sizes, width, height, K, class_aware=False):
         B = len(sizes)
         self.B, self.K, self.sizes = B, int(K), [(int(w), int(h)) for w, h in sizes]
         self.offsets, self.pool_bytes = frame_offsets(self.sizes)
@@ -91,6 +94,9 @@ class BatchPlan:
         self.count_off = _align(self.prob_off + B * self.K * 4)
         self.skip_off = _align(self.count_off + B * 4)
         self.nbytes = _align(self.skip_off + B * 4)
+        if class_aware:
+            self.cls_off = self.nbytes
+            self.nbytes = _align(self.cls_off + B * self.K * 4)
 
     def _samples(self, width, height):
         """the resize samples of the batch (geoms, frefs: one per network input) and the detect descriptors (one per frame)"""
@@ -114,8 +120,22 @@ class BatchPlan:
             host[self.pool_off + off:self.pool_off + off + 3 * w * h] = f.reshape(-1)
 
 
-TILED_CLASS_AWARE = ("{}: class_aware=True is not available with tiles: the cross-tile merge (mdcv_detect_merge_tiles) is class-agnostic "
-                     "and would suppress overlapping boxes of different classes again; a class-aware tile merge is a later change")
+TILED_CLASS_AWARE = ("{}: class_aware=True is not available with the default tile merge: mdcv_detect_merge_tiles is class-agnostic and "
+                     "would suppress overlapping boxes of different classes again; pass tile_merge=\"per_class\" for the class-aware merge")
+TILE_MERGES = _lib.TILE_MERGES
+
+
+def check_tile_merge(who, tiles, class_aware, tile_merge):
+    """the one rule of the `tile_merge` keyword, for the detectors and the functions in front of them: "agnostic" (the default,
+    mdcv_detect_merge_tiles) or "per_class" (mdcv_detect_merge_tiles_mc), which belongs to a tiled, class-aware detector"""
+    if tile_merge not in TILE_MERGES:
+        raise ValueError(f"{who}: tile_merge must be one of {TILE_MERGES}, got {tile_merge!r}")
+    if tile_merge == "per_class" and not tiles:
+        raise ValueError(f"{who}: tile_merge=\"per_class\" is for tiled detection (tiles=True) only")
+    if tile_merge == "per_class" and not class_aware:
+        raise ValueError(f"{who}: tile_merge=\"per_class\" needs class_aware=True (the tiles' detections carry no per-class NMS otherwise)")
+    if tiles and class_aware and tile_merge != "per_class":
+        raise ValueError(TILED_CLASS_AWARE.format(who))
 
 TILE_DESC = 4                            # MDCV_TILE_DESC
 MAX_TILES_PER_FRAME = 64                 # MDCV_TILE_MAX_PER_FRAME
@@ -140,12 +160,12 @@ class TiledBatchPlan(BatchPlan):
     border, the same rounding `sample_geometry` applies; behind the output tables, [src B,K,2 i32].  `first`: the index of the
     batch's first frame in the caller's sequence, for error messages."""
 
-    def __init__(self, sizes, width, height, K, scales, first=0):
+    def __init__(self, sizes, width, height, K, scales, first=0, class_aware=False):
         self.scales = [float(s) for s in scales]
         if len(self.scales) != len(sizes):
             raise ValueError(f"TiledBatchPlan: {len(sizes)} frames but {len(self.scales)} scales")
         self.first = int(first)
-        super().__init__(sizes, width, height, K)
+        super().__init__(sizes, width, height, K, class_aware)
         self.src_off = self.nbytes
         self.nbytes = _align(self.src_off + self.B * self.K * 8)
 
@@ -189,12 +209,12 @@ def _check_frame(f, i):
 class FrameDetections:
     """One frame's result.  boxes float64 [n,4] (x0, y0, x1, y1 in frame coordinates, most confident first), prob float32 [n], rects int32
     [n,4] (the truncated boxes as drawn; (0, 0, -1, -1) for a skipped one), skipped (boxes not drawn), annotated (H, W, 3) uint8 -- a
-    NumPy array, or a device tensor with `keep_on_device`."""
+    NumPy array, or a device tensor with `keep_on_device`, cls int32 [n] (the class of each box; None unless the detector is class-aware)."""
 
-    __slots__ = ("boxes", "prob", "rects", "skipped", "annotated")
+    __slots__ = ("boxes", "prob", "rects", "skipped", "annotated", "cls")
 
-    def __init__(self, boxes, prob, rects, skipped, annotated):
-        self.boxes, self.prob, self.rects, self.skipped, self.annotated = boxes, prob, rects, skipped, annotated
+    def __init__(self, boxes, prob, rects, skipped, annotated, cls=None):
+        self.boxes, self.prob, self.rects, self.skipped, self.annotated, self.cls = boxes, prob, rects, skipped, annotated, cls
 
 
 class TiledFrameDetections(FrameDetections):
@@ -214,7 +234,8 @@ class FrameDetector:
     at most `max_boxes` (<= top_k) boxes per frame are mapped and drawn, the most confident ones; `outline` is the one RGB triple of a
     call (default `ImageColor.getrgb("red")`).  Subclasses override `_plan` (the batch's layout), `_batch_boxes` (the boxes of a batch) and
     `_result_type`; FrameConeDetector also `_annotate` and `_extras`; everything else -- staging, the copy back, the final synchronisation -- is shared.
-    class_aware=True: `detect_postprocess(class_aware=True)` -- class scores, per-class NMS, `prob` the class score."""
+    class_aware=True: `detect_postprocess(class_aware=True)` -- class scores, per-class NMS, `prob` the class score; the
+    results then carry `cls`."""
 
     _result_type = FrameDetections
 
@@ -242,7 +263,7 @@ class FrameDetector:
 
     # -- host half (worker thread): take a batch from the iterable, plan it, pack it into the slot's pinned buffer
     def _plan(self, sizes, first):
-        return BatchPlan(sizes, self.width, self.height, self.top_k)
+        return BatchPlan(sizes, self.width, self.height, self.top_k, self.class_aware)
 
     def _stage(self, it, first, slot):
         frames = [_check_frame(f, first + i) for i, f in enumerate(islice(it, self.batch_size))]
@@ -254,14 +275,21 @@ class FrameDetector:
         return plan, slot
 
     # -- the boxes of a batch, enqueued on `st`: resize from the pool, eval forward, post-process -> device tensors boxes [B,K,4] fp32 in
-    #    the coordinates the plan's detect descriptors map from, prob [B,K], count [B] int32 (capped at max_boxes), src [B,K,2] or None
+    #    the coordinates the plan's detect descriptors map from, prob [B,K], count [B] int32 (capped at max_boxes), src [B,K,2] or None;
+    #    a class-aware detector also leaves the classes [B,K] int32 in the plan's cls table (`_put_cls`)
     def _batch_boxes(self, plan, dbuf, host, pool, st):
         imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
         self.model.eval()
         det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k,
                                  class_aware=self.class_aware)
+        if self.class_aware:
+            self._put_cls(plan, dbuf, det.cls)
         count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
         return det.boxes, det.prob, count, None
+
+    @staticmethod
+    def _put_cls(plan, dbuf, cls):
+        dbuf[plan.cls_off:plan.cls_off + plan.B * plan.K * 4].view(torch.int32).copy_(cls.reshape(-1))
 
     def _draw_boxes(self, plan, dbuf, host, boxes, count, st):
         L, base = _lib.lib(), dbuf.data_ptr()
@@ -300,6 +328,7 @@ class FrameDetector:
         prob = table(plan.prob_off, B * K * 4, np.float32, (B, K))
         cnt = table(plan.count_off, B * 4, np.int32, (B,))
         skipped = table(plan.skip_off, B * 4, np.int32, (B,))
+        cls = table(plan.cls_off, B * K * 4, np.int32, (B, K)) if plan.cls_off is not None else None
         res = []
         for b, (off, (w, h)) in enumerate(zip(plan.offsets, plan.sizes)):
             n = min(int(cnt[b]), K)
@@ -307,7 +336,8 @@ class FrameDetector:
                 ann = pool[off:off + 3 * w * h].view(h, w, 3)
             else:
                 ann = table(plan.pool_off + off, 3 * w * h, np.uint8, (h, w, 3)).copy()      # the pinned buffer is the next batch's
-            r = self._result_type(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann)
+            r = self._result_type(fb[b, :n].copy(), prob[b, :n].copy(), rects[b, :n].copy(), int(skipped[b]), ann,
+                                  None if cls is None else cls[b, :n].copy())
             if plan.src_off is not None:
                 r.src = table(plan.src_off, B * K * 8, np.int32, (B, K, 2))[b, :n].copy()
             add(r, b, n)
@@ -359,8 +389,8 @@ class ConeBatchPlan(BatchPlan):
     """BatchPlan with the cone tables behind it: [total 1 i32] [owner cap,2 i32] [window cap,4 i32] [keypoints cap,7,2 f32]
     [centers cap,7,2 i32] [skipped points B i32], cap = B * per rows, per = min(max_cones, K) crops per frame at most."""
 
-    def __init__(self, sizes, width, height, K, max_cones):
-        super().__init__(sizes, width, height, K)
+    def __init__(self, sizes, width, height, K, max_cones, class_aware=False):
+        super().__init__(sizes, width, height, K, class_aware)
         _append_cone_tables(self, max_cones)
 
 
@@ -379,8 +409,8 @@ def _append_cone_tables(plan, max_cones):
 class TiledConeBatchPlan(TiledBatchPlan):
     """TiledBatchPlan with ConeBatchPlan's tables behind it"""
 
-    def __init__(self, sizes, width, height, K, scales, max_cones, first=0):
-        super().__init__(sizes, width, height, K, scales, first)
+    def __init__(self, sizes, width, height, K, scales, max_cones, first=0, class_aware=False):
+        super().__init__(sizes, width, height, K, scales, first, class_aware)
         _append_cone_tables(self, max_cones)
 
 
@@ -436,7 +466,7 @@ class FrameConeDetector(FrameDetector):
     _result_type = FrameCones
 
     def _plan(self, sizes, first):
-        return ConeBatchPlan(sizes, self.width, self.height, self.top_k, self.max_cones)
+        return ConeBatchPlan(sizes, self.width, self.height, self.top_k, self.max_cones, self.class_aware)
 
     def _annotate(self, plan, slot, dbuf, host, boxes, count, st):
         L = _lib.lib()
@@ -499,11 +529,15 @@ class _Tiled:
     """The tiled front of a detector: the frame is scaled and cut into the tiles training sees (`ImageLabelBatches(ts=True)`), every tile
     goes through the network at its native size, and mdcv_detect_merge_tiles (csrc/detect_tiles.hip) makes the tiles' detections one list
     per frame.  Per batch, on the detector's one stream: all tiles resized from the pool in one launch, the eval forward and
-    `detect_postprocess` in chunks of `tile_batch` tiles, ONE merge launch -- no count is read by the host."""
+    `detect_postprocess` in chunks of `tile_batch` tiles, ONE merge launch -- no count is read by the host.
+    class_aware=True with tile_merge="per_class" (DESIGN.md §35): `detect_postprocess(class_aware=True)` per chunk and
+    mdcv_detect_merge_tiles_mc (csrc/detect_tiles_mc.hip), which removes duplicates -- the seam rule included -- inside a class only and
+    writes the classes straight into the batch's cls table."""
 
-    def _init_tiles(self, scale, tile_batch, contain_thres, class_aware=False):
-        if class_aware:
-            raise ValueError(TILED_CLASS_AWARE.format(type(self).__name__))
+    def _init_tiles(self, scale, tile_batch, contain_thres, class_aware=False, tile_merge="agnostic"):
+        check_tile_merge(type(self).__name__, True, class_aware, tile_merge)
+        self.tile_merge = tile_merge
+        self.class_aware = bool(class_aware)
         if not callable(scale):
             value = float(scale)
             scale = lambda w, h: value                                       # noqa: E731
@@ -519,12 +553,13 @@ class _Tiled:
         return [float(self.scale(w, h)) for w, h in sizes]
 
     def _batch_boxes(self, plan, dbuf, host, pool, st):
-        L = _lib.lib()
+        per_class = self.tile_merge == "per_class"
+        L = _lib.mctiles_lib() if per_class else _lib.lib()
         B, K, NT = plan.B, plan.K, plan.NT
         imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)      # [NT,C,H,W]
         self.model.eval()
         dets = [detect_postprocess(self.model(imgs[at:at + self.tile_batch]), None, self.conf_thres, self.nms_thres, 0.5, self.width,
-                                   self.height, self.top_k) for at in range(0, NT, self.tile_batch)]
+                                   self.height, self.top_k, class_aware=per_class) for at in range(0, NT, self.tile_batch)]
         one = len(dets) == 1
         tboxes = dets[0].boxes if one else torch.cat([d.boxes for d in dets])
         tprob = dets[0].prob if one else torch.cat([d.prob for d in dets])
@@ -534,9 +569,16 @@ class _Tiled:
         prob = torch.empty(B, K, dtype=torch.float32, device=dev)
         src = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
         count = torch.empty(B, dtype=torch.int32, device=dev)
-        L.check(L.detect_merge_tiles(tboxes.data_ptr(), tprob.data_ptr(), tcount.data_ptr(), host.ctypes.data + plan.tile_off,
-                                     dbuf.data_ptr() + plan.tile_off, NT, K, B, self.nms_thres, self.contain_thres, K, boxes.data_ptr(),
-                                     prob.data_ptr(), src.data_ptr(), count.data_ptr(), st.cuda_stream), "detect_merge_tiles")
+        if per_class:
+            tcls = dets[0].cls if one else torch.cat([d.cls for d in dets])
+            L.check(L.detect_merge_tiles_mc(tboxes.data_ptr(), tprob.data_ptr(), tcls.data_ptr(), tcount.data_ptr(),
+                                            host.ctypes.data + plan.tile_off, dbuf.data_ptr() + plan.tile_off, NT, K, B, self.nms_thres,
+                                            self.contain_thres, K, boxes.data_ptr(), prob.data_ptr(), dbuf.data_ptr() + plan.cls_off,
+                                            src.data_ptr(), count.data_ptr(), st.cuda_stream), "detect_merge_tiles_mc")
+        else:
+            L.check(L.detect_merge_tiles(tboxes.data_ptr(), tprob.data_ptr(), tcount.data_ptr(), host.ctypes.data + plan.tile_off,
+                                         dbuf.data_ptr() + plan.tile_off, NT, K, B, self.nms_thres, self.contain_thres, K, boxes.data_ptr(),
+                                         prob.data_ptr(), src.data_ptr(), count.data_ptr(), st.cuda_stream), "detect_merge_tiles")
         if self.max_boxes < self.top_k:
             count = count.clamp(max=self.max_boxes)
         return boxes, prob, count, src
@@ -548,17 +590,18 @@ class TiledFrameDetector(_Tiled, FrameDetector):
     (frame_w, frame_h) -> float (the data set's scales are per camera size).  Boxes of overlapping tiles are merged by the greedy NMS at
     `nms_thres`; `contain_thres` (None: off) also removes a box of one tile that lies to more than that fraction of the smaller area
     inside a more confident box of another tile -- the part of a cone a tile edge cut off.  Yields `TiledFrameDetections` (boxes in
-    frame pixels: merged box / scale).  ONE host synchronisation per batch."""
+    frame pixels: merged box / scale).  ONE host synchronisation per batch.  `tile_merge`: "agnostic" (one NMS over all of a frame's
+    candidates) or, with class_aware=True, "per_class" (class scores, and both rules of the merge inside a class only; `cls` is filled)."""
 
     _result_type = TiledFrameDetections
 
     def __init__(self, model, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 tile_batch=32, contain_thres=None, class_aware=False):
+                 tile_batch=32, contain_thres=None, class_aware=False, tile_merge="agnostic"):
         super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size)
-        self._init_tiles(scale, tile_batch, contain_thres, class_aware)
+        self._init_tiles(scale, tile_batch, contain_thres, class_aware, tile_merge)
 
     def _plan(self, sizes, first):
-        return TiledBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), first)
+        return TiledBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), first, self.class_aware)
 
 
 class TiledFrameConeDetector(_Tiled, FrameConeDetector):
@@ -568,12 +611,13 @@ class TiledFrameConeDetector(_Tiled, FrameConeDetector):
     _result_type = TiledFrameCones
 
     def __init__(self, model, keypoint_net, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0),
-                 batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None, class_aware=False):
+                 batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None, class_aware=False,
+                 tile_merge="agnostic"):
         super().__init__(model, keypoint_net, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, max_cones, bucket, colours)
-        self._init_tiles(scale, tile_batch, contain_thres, class_aware)
+        self._init_tiles(scale, tile_batch, contain_thres, class_aware, tile_merge)
 
     def _plan(self, sizes, first):
-        return TiledConeBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), self.max_cones, first)
+        return TiledConeBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), self.max_cones, first, self.class_aware)
 
 
 # --------------------------------------------------------------------------------------------- the reference's two functions (detect.py)
@@ -592,10 +636,11 @@ def _save(annotated, path):
     return path
 
 
-def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, contain_thres=None, **kw):
+def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, contain_thres=None, tile_merge="agnostic", **kw):
     """`device` is where the reference moves its input (detect.py:78) and where the caller has put the model (detect.py:51): the batches
     are built on the model's device, so the two must be the same GPU.  None: the model's device.  `tiles`: a TiledFrameDetector at
-    `scale` with `contain_thres`; otherwise those two are not looked at."""
+    `scale` with `contain_thres` and `tile_merge`; otherwise the first two are not looked at and tile_merge must be its default."""
+    check_tile_merge("detect", tiles, kw.get("class_aware", False), tile_merge)
     if device is not None:
         want, have = torch.device(device), next(model.parameters()).device
         if want.type != "cuda":
@@ -603,21 +648,22 @@ def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, cont
         if have.type != "cuda" or (want.index is not None and want.index != have.index):
             raise ValueError(f"detect: device {device!r} is not the model's device {str(have)!r}; move the model there first, as the reference's main does")
     if tiles:
-        return TiledFrameDetector(model, scale, conf_thres=conf_thres, nms_thres=nms_thres, contain_thres=contain_thres, **kw)
+        return TiledFrameDetector(model, scale, conf_thres=conf_thres, nms_thres=nms_thres, contain_thres=contain_thres,
+                                  tile_merge=tile_merge, **kw)
     return FrameDetector(model, conf_thres=conf_thres, nms_thres=nms_thres, **kw)
 
 
 def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres, *, tiles=False, scale=1.0, contain_thres=None,
-                      class_aware=False):
+                      class_aware=False, tile_merge="agnostic"):
     """detect.py:60-111 for one RGB image file: mode 'image' saves under `output_path` with the file's own name, any other mode saves over
     `target_path` (the reference's rule for its dumped video frames); the saved path is returned.  With no detection the image is
     saved unannotated.  `device` must be the GPU the model is on (or None).  Each call builds its own detector: for many files use `detect`
     on their directory.  Keyword-only `tiles=True`: tile-and-scale inference at `scale` (TiledFrameDetector), the counterpart of training
-    with ts=True; the defaults are the reference's whole-frame pad and resize.  `class_aware`: FrameDetector's (not with tiles)."""
-    if tiles and class_aware:
-        raise ValueError(TILED_CLASS_AWARE.format("single_img_detect(tiles=True)"))
+    with ts=True; the defaults are the reference's whole-frame pad and resize.  `class_aware`: FrameDetector's; with tiles it needs
+    `tile_merge="per_class"` (TiledFrameDetector's)."""
+    check_tile_merge("single_img_detect", tiles, class_aware, tile_merge)
     frame = _open_rgb(target_path)
-    det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=1, class_aware=class_aware)
+    det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=1, class_aware=class_aware)
     res = next(iter(det.detect_frames([frame])))
     if mode == "image":
         return _save(res.annotated, os.path.join(output_path, target_path.split("/")[-1]))
@@ -625,19 +671,19 @@ def single_img_detect(target_path, output_path, mode, model, device, conf_thres,
 
 
 def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16, *, tiles=False, scale=1.0, contain_thres=None,
-           class_aware=False):
+           class_aware=False, tile_merge="agnostic"):
     """detect.py:113-196.  An image file (.jpg / .jpeg / .png / .tif) goes through `single_img_detect`; a directory has its image files,
     sorted by name, detected in batches of `batch_size` and written to `output_path` under their own names (-> the list of paths).
     Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead.
-    Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`: as in `single_img_detect`."""
-    if tiles and class_aware:
-        raise ValueError(TILED_CLASS_AWARE.format("detect(tiles=True)"))
+    Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`, `tile_merge`: as in `single_img_detect`."""
+    check_tile_merge("detect", tiles, class_aware, tile_merge)
     ext = os.path.splitext(target_path)[-1].lower()
     if os.path.isdir(target_path):
         names = sorted(f for f in os.listdir(target_path)
                        if os.path.splitext(f)[-1].lower() in IMG_FORMATS and os.path.isfile(os.path.join(target_path, f)))
         print(f"Detection Mode is: directory ({len(names)} images)")
-        det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, batch_size=batch_size, class_aware=class_aware)
+        det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=batch_size,
+                        class_aware=class_aware)
         frames = (_open_rgb(os.path.join(target_path, f)) for f in names)
         paths = [_save(res.annotated, os.path.join(output_path, f)) for f, res in zip(names, det.detect_frames(frames))]
         print(f"Please check output images at {output_path}")
@@ -651,6 +697,6 @@ def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch
     print("Detection Mode is: image")
     path = single_img_detect(target_path=target_path, output_path=output_path, mode="image", model=model, device=device,
                              conf_thres=conf_thres, nms_thres=nms_thres, tiles=tiles, scale=scale, contain_thres=contain_thres,
-                             class_aware=class_aware)
+                             class_aware=class_aware, tile_merge=tile_merge)
     print(f"Please check output image at {path}")
     return path

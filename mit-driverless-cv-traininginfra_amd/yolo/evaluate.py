@@ -13,7 +13,9 @@ in a fixed order), so two runs -- or any split of the same images into batches -
     r = ap.result();  r.AP, r.AP50, r.AP50_by_range
 
 `python -m mdcv.yolo.evaluate --model_cfg ... --weights_path ...` evaluates the cfg's validation CSV; with `--frames DIR --labels CSV`
-it scores whole frames (`--tiles --scale s`: through TiledFrameDetector) against the CSV's boxes in frame pixels.
+it scores whole frames (`--tiles --scale s`: through TiledFrameDetector; `--class_aware --tile_merge per_class`: its class-aware merge,
+DESIGN.md §35) against the CSV's boxes in frame pixels.  Labels with classes go through `evaluate_frames(..., label_classes=, num_classes=)`
+or `DatasetAP.add_frames(..., classes=)`: the frame results' `cls` is then matched class by class.
 """
 import math
 import time
@@ -176,13 +178,24 @@ class DatasetAP:
         self._match(boxes, prob, cls, count, GT_PIXELS, gt_boxes, gt_cls, gt_ignore, gt_count, T, 1.0, 1.0)
 
     @staticmethod
-    def pack_frames(results, labels, K, scale=None, ignore=None):
+    def pack_frames(results, labels, K, scale=None, ignore=None, classes=None):
         """the host half of `add_frames` -> boxes [B,K,4] f32, prob [B,K] f32, count [B] i32, gt [B,T,4] f32, gt_count [B] i32, gt_ignore
-        [B,T] u8.  A frame with more than K boxes keeps the first K (they are most confident first)."""
+        [B,T] u8.  A frame with more than K boxes keeps the first K (they are most confident first).  With `classes` (per frame the [n]
+        classes of its labels) two more: cls [B,K] i32 from the results' `cls`, gt_cls [B,T] i32; both zero past the counts."""
         results, labels = list(results), [np.asarray(l, np.float64).reshape(-1, 4) for l in labels]
         if len(results) != len(labels) or (ignore is not None and len(ignore) != len(labels)):
             raise ValueError("add_frames: one label array (and one ignore array) per frame")
         B, T = len(results), max([len(l) for l in labels] + [1])
+        if classes is not None:
+            classes = [np.asarray(c).reshape(-1) for c in classes]
+            if len(classes) != B or any(len(c) != len(l) or (len(c) and c.dtype.kind not in "iu") for c, l in zip(classes, labels)):
+                raise ValueError("add_frames: classes needs one integer array per frame, one class per label row")
+            if any(r.cls is None for r in results):
+                raise ValueError("add_frames: classes were given but a result has cls None: build the detector with class_aware=True")
+            cls, gt_cls = np.zeros((B, K), np.int32), np.zeros((B, T), np.int32)
+            for b, (r, c) in enumerate(zip(results, classes)):
+                n = min(len(r.boxes), K)
+                cls[b, :n], gt_cls[b, :len(c)] = np.asarray(r.cls)[:n], c
         boxes, prob, count = np.zeros((B, K, 4), np.float32), np.zeros((B, K), np.float32), np.zeros(B, np.int32)
         gt, gt_count, gt_ignore = np.zeros((B, T, 4), np.float32), np.zeros(B, np.int32), np.zeros((B, T), np.uint8)
         for b, (r, l) in enumerate(zip(results, labels)):
@@ -192,14 +205,15 @@ class DatasetAP:
             gt_count[b] = len(l)
             if ignore is not None:
                 gt_ignore[b, :len(l)] = np.asarray(ignore[b]).reshape(-1) != 0
-        return boxes, prob, count, gt, gt_count, gt_ignore
+        return (boxes, prob, count, gt, gt_count, gt_ignore) + (() if classes is None else (cls, gt_cls))
 
-    def add_frames(self, results, labels, scale=None, ignore=None):
+    def add_frames(self, results, labels, scale=None, ignore=None, classes=None):
         """results: `FrameDetections` / `TiledFrameDetections` of some frames; labels: per frame an [n,4] array of corner boxes
         (x0, y0, x1, y1) in the coordinates of the results' boxes -- frame pixels for FrameDetector, scaled-frame pixels for the tiled
         detectors, for which `scale=` multiplies the frame-pixel labels on the host (float64) before the upload.  ignore: per frame
-        [n] flags.  Class 0.  Packed into one pinned buffer, one asynchronous copy, one launch."""
-        arrays = self.pack_frames(results, labels, self.K, scale, ignore)
+        [n] flags.  classes: per frame the [n] integer classes of its labels; the results' `cls` (a class-aware detector's) and these
+        are then matched class by class; without, class 0.  Packed into one pinned buffer, one asynchronous copy, one launch."""
+        arrays = self.pack_frames(results, labels, self.K, scale, ignore, classes)
         if len(arrays[0]) == 0:
             return
         sizes = [(a.nbytes + 15) // 16 * 16 for a in arrays]
@@ -215,8 +229,9 @@ class DatasetAP:
             dt = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8}[a.dtype]
             views.append(dbuf[at:at + a.nbytes].view(dt).view(a.shape))
             at += n
-        boxes, prob, count, gt, gt_count, gt_ignore = views
-        self.add_boxes(boxes, prob, None, count, gt, None, gt_count, gt_ignore)
+        boxes, prob, count, gt, gt_count, gt_ignore = views[:6]
+        cls, gt_cls = views[6:] if classes is not None else (None, None)
+        self.add_boxes(boxes, prob, cls, count, gt, gt_cls, gt_count, gt_ignore)
 
     def result(self):
         """finalize and the evaluator's one read-back -> `APResult`"""
@@ -282,23 +297,33 @@ def evaluate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=F
 
 
 def evaluate_frames(frames, labels, detector, scale=None, area_ranges=((0.0, math.inf),), iou_thresholds=COCO_IOU_THRESHOLDS, batch=64,
-                    class_aware=None):
+                    class_aware=None, label_classes=None, num_classes=None):
     """whole frames through a `FrameDetector` / `TiledFrameDetector` against per-frame corner boxes in frame pixels -> APResult.
     scale: the tiled detector's constant scale (its boxes are in scaled-frame pixels, so the labels are multiplied by it).
-    class_aware: None leaves the detector as it was built; True / False must agree with the detector's own `class_aware` (the labels
-    carry no class, so every box is scored as class 0 either way: what changes is which boxes the detector keeps)."""
+    class_aware: None leaves the detector as it was built; True / False must agree with the detector's own `class_aware`.
+    label_classes: per frame the [n] integer classes of its labels -- the detector must then be class-aware, and its boxes are scored
+    class by class over `num_classes` classes (default 1); without, every box is scored as class 0, and class_aware only changes which
+    boxes the detector keeps."""
     if class_aware is not None and bool(class_aware) != bool(getattr(detector, "class_aware", False)):
         raise ValueError(f"evaluate_frames: class_aware={class_aware!r} but the detector was built with class_aware={getattr(detector, 'class_aware', False)!r}")
     labels = list(labels)
-    acc = DatasetAP(1, max(len(labels), 1), top_k=detector.top_k, iou_thresholds=iou_thresholds, area_ranges=area_ranges, device=detector.device)
+    label_classes = None if label_classes is None else list(label_classes)
+    if label_classes is not None and len(label_classes) != len(labels):
+        raise ValueError(f"evaluate_frames: {len(labels)} label arrays but {len(label_classes)} arrays of label classes")
+    acc = DatasetAP(1 if num_classes is None else int(num_classes), max(len(labels), 1), top_k=detector.top_k, iou_thresholds=iou_thresholds,
+                    area_ranges=area_ranges, device=detector.device)
     pending = []
+
+    def flush():
+        lo, hi = acc.n_images, acc.n_images + len(pending)
+        acc.add_frames(pending, labels[lo:hi], scale=scale, classes=None if label_classes is None else label_classes[lo:hi])
     for r in detector.detect_frames(frames):
         pending.append(r)
         if len(pending) == batch:
-            acc.add_frames(pending, labels[acc.n_images:acc.n_images + batch], scale=scale)
+            flush()
             pending = []
     if pending:
-        acc.add_frames(pending, labels[acc.n_images:acc.n_images + len(pending)], scale=scale)
+        flush()
     return acc.result()
 
 
@@ -320,7 +345,10 @@ def main(argv=None):
     p.add_argument('--conf_thres', type=float, default=None, help='frame mode: confidence threshold (default: the cfg\'s)')
     p.add_argument('--nms_thres', type=float, default=None, help='frame mode: NMS threshold (default: the cfg\'s)')
     p.add_argument('--precision', type=str, default=None, choices=["bf16", "fp32"], help='precision of the network (default: the model\'s)')
-    p.add_argument('--class_aware', action='store_true', help='class scores, per-class NMS and class-restricted matching (not with --tiles)')
+    p.add_argument('--class_aware', action='store_true',
+                   help='class scores, per-class NMS and class-restricted matching (with --tiles: together with --tile_merge per_class)')
+    p.add_argument('--tile_merge', type=str, default="agnostic", choices=["agnostic", "per_class"],
+                   help='frame mode with --tiles: the cross-tile merge; per_class (needs --class_aware) removes duplicates inside a class only')
     a = p.parse_args(argv)
     device = torch.device("cuda", torch.cuda.current_device())
     model = Darknet(config_path=a.model_cfg, xy_loss=2, wh_loss=1.6, no_object_loss=25, object_loss=0.1, vanilla_anchor=False, precision=a.precision)
@@ -338,7 +366,8 @@ def main(argv=None):
     from .detect import _detector, _open_rgb
     rows = read_label_csv(a.labels, a.frames)
     labels = [np.stack([b[:, 0], b[:, 1], b[:, 0] + b[:, 3], b[:, 1] + b[:, 2]], axis=1).astype(np.float64) for *_x, b in rows]   # (x, y, h, w)
-    det = _detector(model, device, a.conf_thres, a.nms_thres, a.tiles, a.scale, a.contain_thres, batch_size=a.batch_size, class_aware=a.class_aware)
+    det = _detector(model, device, a.conf_thres, a.nms_thres, a.tiles, a.scale, a.contain_thres, a.tile_merge, batch_size=a.batch_size,
+                    class_aware=a.class_aware)
     frames = (_open_rgb(os.path.join(a.frames, os.path.basename(r[0]))) for r in rows)
     res = evaluate_frames(frames, labels, det, scale=a.scale if a.tiles else None, class_aware=a.class_aware,
                           area_ranges=((0.0, math.inf), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, math.inf)))
