@@ -2,7 +2,8 @@
 DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`), of
 libmdcv_box.so (its opt-in box loss: `box_lib()`), of libmdcv_ign.so (the opt-in prediction-IoU ignore rule of its
 no-object term: `ign_lib()`), of libmdcv_mcdet.so (the opt-in class-aware detection post-processing: `mcdet_lib()`,
-DESIGN §34) and of libmdcv_mctiles.so (the opt-in class-aware cross-tile merge: `mctiles_lib()`).
+DESIGN §34), of libmdcv_mctiles.so (the opt-in class-aware cross-tile merge: `mctiles_lib()`) and of libmdcv_softnms.so
+(the opt-in Soft-NMS post-processing: `softnms_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -42,6 +43,10 @@ MCDET_MAX_CLASSES = 65535                        # include/mdcv_mcdet.h MDCV_MCD
 MCTILES_HEADER = os.path.join(ROOT, "include", "mdcv_mctiles.h")
 MCTILES_LIB_PATH = os.path.join(_HERE, "libmdcv_mctiles.so")
 TILE_MERGES = ("agnostic", "per_class")          # the cross-tile merge of the tiled detectors: mdcv_detect_merge_tiles / _mc
+
+SOFTNMS_HEADER = os.path.join(ROOT, "include", "mdcv_softnms.h")
+SOFTNMS_LIB_PATH = os.path.join(_HERE, "libmdcv_softnms.so")
+NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}   # include/mdcv_softnms.h MDCV_SNMS_HARD / _LINEAR / _GAUSSIAN
 
 F32, BF16 = 0, 1
 
@@ -208,6 +213,27 @@ def mctiles_lib():
     if _mctiles is None:
         _mctiles = _Lib(MCTILES_LIB_PATH, MCTILES_HEADER, "libmdcv_mctiles")
     return _mctiles
+
+
+_softnms = None
+
+
+def softnms_lib():
+    """libmdcv_softnms.so behind include/mdcv_softnms.h: the same binding and `check`, loaded on first use -- by a
+    post-processing call or an nms() with a soft method, or by soft_nms(), only"""
+    global _softnms
+    if _softnms is None:
+        _softnms = _Lib(SOFTNMS_LIB_PATH, SOFTNMS_HEADER, "libmdcv_softnms")
+    return _softnms
+
+
+def nms_method(who, name, sigma=0.5):
+    """the method's code; an unknown name, or a sigma that is not a positive finite number with "gaussian", is a ValueError"""
+    if name not in NMS_METHODS:
+        raise ValueError(f"{who}: nms method must be one of {sorted(NMS_METHODS)}, got {name!r}")
+    if name == "gaussian" and not 0.0 < float(sigma) < float("inf"):
+        raise ValueError(f"{who}: sigma must be a positive finite number with the gaussian nms method, got {sigma!r}")
+    return NMS_METHODS[name]
 
 
 def pred_ignore(value):

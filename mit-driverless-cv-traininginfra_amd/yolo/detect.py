@@ -122,7 +122,16 @@ class BatchPlan:
 
 TILED_CLASS_AWARE = ("{}: class_aware=True is not available with the default tile merge: mdcv_detect_merge_tiles is class-agnostic and "
                      "would suppress overlapping boxes of different classes again; pass tile_merge=\"per_class\" for the class-aware merge")
+TILED_SOFT_NMS = ("{}: nms={!r} is not available with tiles: the cross-tile merge (mdcv_detect_merge_tiles) is a hard NMS and would remove "
+                  "the overlapping boxes a soft method kept; use nms=\"hard\" with tiles, or a whole-frame detector")
 TILE_MERGES = _lib.TILE_MERGES
+
+
+def check_nms(who, tiles, nms, sigma):
+    """the one rule of the `nms` keyword: a method of `detect_postprocess`, and a soft one only without tiles"""
+    _lib.nms_method(who, nms, sigma)
+    if tiles and nms != "hard":
+        raise ValueError(TILED_SOFT_NMS.format(who, nms))
 
 
 def check_tile_merge(who, tiles, class_aware, tile_merge):
@@ -235,12 +244,15 @@ class FrameDetector:
     call (default `ImageColor.getrgb("red")`).  Subclasses override `_plan` (the batch's layout), `_batch_boxes` (the boxes of a batch) and
     `_result_type`; FrameConeDetector also `_annotate` and `_extras`; everything else -- staging, the copy back, the final synchronisation -- is shared.
     class_aware=True: `detect_postprocess(class_aware=True)` -- class scores, per-class NMS, `prob` the class score; the
-    results then carry `cls`."""
+    results then carry `cls`.  nms="linear" / "gaussian" with `sigma`: `detect_postprocess`'s Soft-NMS, `prob`
+    the decayed score, the scan ending at conf_thres."""
 
     _result_type = FrameDetections
 
     def __init__(self, model, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 class_aware=False):
+                 class_aware=False, nms="hard", sigma=0.5):
+        check_nms(type(self).__name__, isinstance(self, _Tiled), nms, sigma)
+        self.nms, self.sigma = nms, float(sigma)
         conf, nms, _ = model.get_threshs()
         self.model = model
         self.class_aware = bool(class_aware)
@@ -281,7 +293,7 @@ class FrameDetector:
         imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)
         self.model.eval()
         det = detect_postprocess(self.model(imgs), None, self.conf_thres, self.nms_thres, 0.5, self.width, self.height, self.top_k,
-                                 class_aware=self.class_aware)
+                                 class_aware=self.class_aware, nms=self.nms, sigma=self.sigma)
         if self.class_aware:
             self._put_cls(plan, dbuf, det.cls)
         count = det.count if self.max_boxes >= self.top_k else det.count.clamp(max=self.max_boxes)
@@ -448,8 +460,8 @@ class FrameConeDetector(FrameDetector):
     `detect_frames(..., return_crops=True)` also copies the crops back (a third synchronisation; tests and debugging)."""
 
     def __init__(self, model, keypoint_net, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, class_aware=False):
-        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, class_aware)
+                 max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, class_aware=False, nms="hard", sigma=0.5):
+        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, class_aware, nms, sigma)
         self.keypoint_net = keypoint_net
         self.max_cones, self.bucket = int(max_cones), int(bucket)
         if self.max_cones < 1 or self.bucket < 1:
@@ -596,8 +608,8 @@ class TiledFrameDetector(_Tiled, FrameDetector):
     _result_type = TiledFrameDetections
 
     def __init__(self, model, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 tile_batch=32, contain_thres=None, class_aware=False, tile_merge="agnostic"):
-        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size)
+                 tile_batch=32, contain_thres=None, class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5):
+        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, nms=nms, sigma=sigma)
         self._init_tiles(scale, tile_batch, contain_thres, class_aware, tile_merge)
 
     def _plan(self, sizes, first):
@@ -612,8 +624,9 @@ class TiledFrameConeDetector(_Tiled, FrameConeDetector):
 
     def __init__(self, model, keypoint_net, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0),
                  batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None, class_aware=False,
-                 tile_merge="agnostic"):
-        super().__init__(model, keypoint_net, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, max_cones, bucket, colours)
+                 tile_merge="agnostic", nms="hard", sigma=0.5):
+        super().__init__(model, keypoint_net, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, max_cones, bucket, colours,
+                         nms=nms, sigma=sigma)
         self._init_tiles(scale, tile_batch, contain_thres, class_aware, tile_merge)
 
     def _plan(self, sizes, first):
@@ -641,6 +654,7 @@ def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, cont
     are built on the model's device, so the two must be the same GPU.  None: the model's device.  `tiles`: a TiledFrameDetector at
     `scale` with `contain_thres` and `tile_merge`; otherwise the first two are not looked at and tile_merge must be its default."""
     check_tile_merge("detect", tiles, kw.get("class_aware", False), tile_merge)
+    check_nms("detect", tiles, kw.get("nms", "hard"), kw.get("sigma", 0.5))
     if device is not None:
         want, have = torch.device(device), next(model.parameters()).device
         if want.type != "cuda":
@@ -654,16 +668,18 @@ def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, cont
 
 
 def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres, *, tiles=False, scale=1.0, contain_thres=None,
-                      class_aware=False, tile_merge="agnostic"):
+                      class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5):
     """detect.py:60-111 for one RGB image file: mode 'image' saves under `output_path` with the file's own name, any other mode saves over
     `target_path` (the reference's rule for its dumped video frames); the saved path is returned.  With no detection the image is
     saved unannotated.  `device` must be the GPU the model is on (or None).  Each call builds its own detector: for many files use `detect`
     on their directory.  Keyword-only `tiles=True`: tile-and-scale inference at `scale` (TiledFrameDetector), the counterpart of training
     with ts=True; the defaults are the reference's whole-frame pad and resize.  `class_aware`: FrameDetector's; with tiles it needs
-    `tile_merge="per_class"` (TiledFrameDetector's)."""
+    `tile_merge="per_class"` (TiledFrameDetector's).  `nms`, `sigma`: FrameDetector's; a soft method is for tiles=False."""
     check_tile_merge("single_img_detect", tiles, class_aware, tile_merge)
+    check_nms("single_img_detect", tiles, nms, sigma)
     frame = _open_rgb(target_path)
-    det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=1, class_aware=class_aware)
+    det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=1, class_aware=class_aware,
+                    nms=nms, sigma=sigma)
     res = next(iter(det.detect_frames([frame])))
     if mode == "image":
         return _save(res.annotated, os.path.join(output_path, target_path.split("/")[-1]))
@@ -671,19 +687,20 @@ def single_img_detect(target_path, output_path, mode, model, device, conf_thres,
 
 
 def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16, *, tiles=False, scale=1.0, contain_thres=None,
-           class_aware=False, tile_merge="agnostic"):
+           class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5):
     """detect.py:113-196.  An image file (.jpg / .jpeg / .png / .tif) goes through `single_img_detect`; a directory has its image files,
     sorted by name, detected in batches of `batch_size` and written to `output_path` under their own names (-> the list of paths).
     Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead.
-    Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`, `tile_merge`: as in `single_img_detect`."""
+    Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`, `tile_merge`, `nms`, `sigma`: as in `single_img_detect`."""
     check_tile_merge("detect", tiles, class_aware, tile_merge)
+    check_nms("detect", tiles, nms, sigma)
     ext = os.path.splitext(target_path)[-1].lower()
     if os.path.isdir(target_path):
         names = sorted(f for f in os.listdir(target_path)
                        if os.path.splitext(f)[-1].lower() in IMG_FORMATS and os.path.isfile(os.path.join(target_path, f)))
         print(f"Detection Mode is: directory ({len(names)} images)")
         det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=batch_size,
-                        class_aware=class_aware)
+                        class_aware=class_aware, nms=nms, sigma=sigma)
         frames = (_open_rgb(os.path.join(target_path, f)) for f in names)
         paths = [_save(res.annotated, os.path.join(output_path, f)) for f, res in zip(names, det.detect_frames(frames))]
         print(f"Please check output images at {output_path}")
@@ -697,6 +714,6 @@ def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch
     print("Detection Mode is: image")
     path = single_img_detect(target_path=target_path, output_path=output_path, mode="image", model=model, device=device,
                              conf_thres=conf_thres, nms_thres=nms_thres, tiles=tiles, scale=scale, contain_thres=contain_thres,
-                             class_aware=class_aware, tile_merge=tile_merge)
+                             class_aware=class_aware, tile_merge=tile_merge, nms=nms, sigma=sigma)
     print(f"Please check output image at {path}")
     return path

@@ -261,10 +261,10 @@ class DatasetAP:
 
 
 def evaluate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=False, top_k=200, iou_thresholds=COCO_IOU_THRESHOLDS,
-             area_ranges=((0.0, math.inf), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, math.inf)), class_aware=False):
+             area_ranges=((0.0, math.inf), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, math.inf)), class_aware=False, nms="hard", sigma=0.5):
     """`validate`'s loop with a `DatasetAP` beside the per-image statistics: one more launch per batch, nothing more read per batch.
     -> ((mean_mAP, mean_R, mean_P, seconds_per_image) exactly as `validate` returns them, APResult).  Prints validate's line, then one
-    line of AP@[.5:.95], AP50 and AP50 per area range (box areas in network-input px^2).  class_aware: `detect_postprocess`'s keyword."""
+    line of AP@[.5:.95], AP50 and AP50 per area range (box areas in network-input px^2).  class_aware, nms, sigma: `detect_postprocess`'s keywords."""
     with torch.no_grad():
         t_start = time.time()
         conf_thres, nms_thres, iou_thres = model.get_threshs()
@@ -277,7 +277,8 @@ def evaluate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=F
         for _uris, imgs, targets in dataloader:
             imgs = imgs.to(device, non_blocking=True)
             targets = targets.to(device, non_blocking=True)
-            det = detect_postprocess(model(imgs), targets, conf_thres, nms_thres, iou_thres, width, height, top_k, class_aware=class_aware)
+            det = detect_postprocess(model(imgs), targets, conf_thres, nms_thres, iou_thres, width, height, top_k, class_aware=class_aware,
+                                     nms=nms, sigma=sigma)
             stats.append(det.stats)
             acc.add(det, targets, width, height)
         if stats:
@@ -349,6 +350,9 @@ def main(argv=None):
                    help='class scores, per-class NMS and class-restricted matching (with --tiles: together with --tile_merge per_class)')
     p.add_argument('--tile_merge', type=str, default="agnostic", choices=["agnostic", "per_class"],
                    help='frame mode with --tiles: the cross-tile merge; per_class (needs --class_aware) removes duplicates inside a class only')
+    p.add_argument('--nms', type=str, default="hard", choices=["hard", "linear", "gaussian"],
+                   help='the suppression rule: greedy hard NMS, or Soft-NMS with a linear or Gaussian score decay (not with --tiles)')
+    p.add_argument('--nms_sigma', type=float, default=0.5, help='--nms gaussian: the decay is exp(-IoU^2 / sigma)')
     a = p.parse_args(argv)
     device = torch.device("cuda", torch.cuda.current_device())
     model = Darknet(config_path=a.model_cfg, xy_loss=2, wh_loss=1.6, no_object_loss=25, object_loss=0.1, vanilla_anchor=False, precision=a.precision)
@@ -361,13 +365,13 @@ def main(argv=None):
         width, height = model.img_size()
         loader = ImageLabelBatches(model.get_links()[0], a.dataset_path, width, height, num_images=model.num_images()[0], bw=model.get_bw(),
                                    ts=a.ts, batch_size=a.batch_size, shuffle=False, device=device)
-        return evaluate(dataloader=loader, model=model, device=device, class_aware=a.class_aware)[1]
+        return evaluate(dataloader=loader, model=model, device=device, class_aware=a.class_aware, nms=a.nms, sigma=a.nms_sigma)[1]
     from ..data.images.labels import read_label_csv
     from .detect import _detector, _open_rgb
     rows = read_label_csv(a.labels, a.frames)
     labels = [np.stack([b[:, 0], b[:, 1], b[:, 0] + b[:, 3], b[:, 1] + b[:, 2]], axis=1).astype(np.float64) for *_x, b in rows]   # (x, y, h, w)
     det = _detector(model, device, a.conf_thres, a.nms_thres, a.tiles, a.scale, a.contain_thres, a.tile_merge, batch_size=a.batch_size,
-                    class_aware=a.class_aware)
+                    class_aware=a.class_aware, nms=a.nms, sigma=a.nms_sigma)
     frames = (_open_rgb(os.path.join(a.frames, os.path.basename(r[0]))) for r in rows)
     res = evaluate_frames(frames, labels, det, scale=a.scale if a.tiles else None, class_aware=a.class_aware,
                           area_ranges=((0.0, math.inf), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, math.inf)))

@@ -4,7 +4,7 @@ Same keyword signature and return tuple `(mean_mAP, mean_R, mean_P, seconds_per_
 (conf filter -> NMS -> IoU matching -> AP, validate.py:80-141) runs on the device for the whole batch
 (`postprocess.detect_postprocess`); per-image statistics stay in HBM until the single read-back at the end.
 `class_aware=True` (keyword, off by default) validates a multi-class detector: class scores, per-class NMS and class-restricted label
-matching.
+matching.  `nms="linear"` / `"gaussian"` with `sigma` (keywords, "hard" by default) validates with Soft-NMS.
 The image-drawing / upload branch (validate.py:139-160, PIL + gsutil) is visualisation and is not part of this path.
 """
 import time
@@ -14,7 +14,7 @@ import torch
 from .postprocess import detect_postprocess
 
 
-def validate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=False, class_aware=False):
+def validate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=False, class_aware=False, nms="hard", sigma=0.5):
     with torch.no_grad():
         t_start = time.time()
         conf_thres, nms_thres, iou_thres = model.get_threshs()
@@ -27,7 +27,7 @@ def validate(*, dataloader, model, device, step=-1, bbox_all=False, debug_mode=F
             targets = targets.to(device, non_blocking=True)
             output = model(imgs)
             stats.append(detect_postprocess(output, targets, conf_thres, nms_thres, iou_thres, width, height,
-                                            class_aware=class_aware).stats)
+                                            class_aware=class_aware, nms=nms, sigma=sigma).stats)
         if stats:
             s = torch.cat(stats, 0)
             valid = s[:, 3] > 0
