@@ -2,8 +2,9 @@
 DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class loss of the YOLO head: `cls_lib()`), of
 libmdcv_box.so (its opt-in box loss: `box_lib()`), of libmdcv_ign.so (the opt-in prediction-IoU ignore rule of its
 no-object term: `ign_lib()`), of libmdcv_mcdet.so (the opt-in class-aware detection post-processing: `mcdet_lib()`,
-DESIGN §34), of libmdcv_mctiles.so (the opt-in class-aware cross-tile merge: `mctiles_lib()`) and of libmdcv_softnms.so
-(the opt-in Soft-NMS post-processing: `softnms_lib()`).
+DESIGN §34), of libmdcv_mctiles.so (the opt-in class-aware cross-tile merge: `mctiles_lib()`), of libmdcv_softnms.so
+(the opt-in Soft-NMS post-processing: `softnms_lib()`) and of libmdcv_softtiles.so (the opt-in soft cross-tile merge:
+`softtiles_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -42,10 +43,14 @@ MCDET_MAX_CLASSES = 65535                        # include/mdcv_mcdet.h MDCV_MCD
 
 MCTILES_HEADER = os.path.join(ROOT, "include", "mdcv_mctiles.h")
 MCTILES_LIB_PATH = os.path.join(_HERE, "libmdcv_mctiles.so")
-TILE_MERGES = ("agnostic", "per_class")          # the cross-tile merge of the tiled detectors: mdcv_detect_merge_tiles / _mc
+# the cross-tile merge of the tiled detectors: mdcv_detect_merge_tiles / _mc, and mdcv_detect_merge_tiles_soft without / with classes
+TILE_MERGES = ("agnostic", "per_class", "soft", "soft_per_class")
+SOFT_TILE_MERGES = ("soft", "soft_per_class")
 
 SOFTNMS_HEADER = os.path.join(ROOT, "include", "mdcv_softnms.h")
 SOFTNMS_LIB_PATH = os.path.join(_HERE, "libmdcv_softnms.so")
+SOFTTILES_HEADER = os.path.join(ROOT, "include", "mdcv_softtiles.h")
+SOFTTILES_LIB_PATH = os.path.join(_HERE, "libmdcv_softtiles.so")
 NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}   # include/mdcv_softnms.h MDCV_SNMS_HARD / _LINEAR / _GAUSSIAN
 
 F32, BF16 = 0, 1
@@ -225,6 +230,18 @@ def softnms_lib():
     if _softnms is None:
         _softnms = _Lib(SOFTNMS_LIB_PATH, SOFTNMS_HEADER, "libmdcv_softnms")
     return _softnms
+
+
+_softtiles = None
+
+
+def softtiles_lib():
+    """libmdcv_softtiles.so behind include/mdcv_softtiles.h: the same binding and `check`, loaded on first use -- by a tiled
+    detector built with tile_merge="soft" / "soft_per_class" only"""
+    global _softtiles
+    if _softtiles is None:
+        _softtiles = _Lib(SOFTTILES_LIB_PATH, SOFTTILES_HEADER, "libmdcv_softtiles")
+    return _softtiles
 
 
 def nms_method(who, name, sigma=0.5):

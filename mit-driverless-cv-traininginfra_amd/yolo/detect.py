@@ -22,7 +22,8 @@ outlines and key-point discs drawn on the device).
 
 `TiledFrameDetector` / `TiledFrameConeDetector` run the same interface on the tiles training sees (`ts=True`): every tile at its native
 scale through the network, the tiles' detections merged per frame by `mdcv_detect_merge_tiles` (csrc/detect_tiles.hip) or,
-for a class-aware detector with `tile_merge="per_class"`, class by class by `mdcv_detect_merge_tiles_mc` (csrc/detect_tiles_mc.hip; §35).
+for a class-aware detector with `tile_merge="per_class"`, class by class by `mdcv_detect_merge_tiles_mc` (csrc/detect_tiles_mc.hip; §35),
+or, with a soft `nms` and `tile_merge="soft"` / `"soft_per_class"`, by `mdcv_detect_merge_tiles_soft` (csrc/detect_tiles_soft.hip; §37).
 
 `single_img_detect` and `detect` take the reference's argument lists, so a caller swaps the import.  Departures, all
 documented in DESIGN.md §19: a box Pillow would refuse (x1 < x0, y1 < y0) or C could not convert (NaN, inf, magnitude >= 2^30) is skipped
@@ -123,27 +124,36 @@ class BatchPlan:
 TILED_CLASS_AWARE = ("{}: class_aware=True is not available with the default tile merge: mdcv_detect_merge_tiles is class-agnostic and "
                      "would suppress overlapping boxes of different classes again; pass tile_merge=\"per_class\" for the class-aware merge")
 TILED_SOFT_NMS = ("{}: nms={!r} is not available with tiles: the cross-tile merge (mdcv_detect_merge_tiles) is a hard NMS and would remove "
-                  "the overlapping boxes a soft method kept; use nms=\"hard\" with tiles, or a whole-frame detector")
+                  "the overlapping boxes a soft method kept; use nms=\"hard\" with tiles, or a whole-frame detector, or the soft merge: "
+                  "tile_merge=\"soft\" (with class_aware=True: \"soft_per_class\")")
 TILE_MERGES = _lib.TILE_MERGES
+SOFT_TILE_MERGES = _lib.SOFT_TILE_MERGES
 
 
-def check_nms(who, tiles, nms, sigma):
-    """the one rule of the `nms` keyword: a method of `detect_postprocess`, and a soft one only without tiles"""
+def check_nms(who, tiles, nms, sigma, tile_merge="agnostic"):
+    """the one rule of the `nms` keyword: a method of `detect_postprocess`; with tiles a soft one goes with a soft `tile_merge`
+    (mdcv_detect_merge_tiles_soft) and a soft `tile_merge` with a soft one"""
     _lib.nms_method(who, nms, sigma)
-    if tiles and nms != "hard":
+    if tiles and nms != "hard" and tile_merge not in SOFT_TILE_MERGES:
         raise ValueError(TILED_SOFT_NMS.format(who, nms))
+    if tile_merge in SOFT_TILE_MERGES and nms == "hard":
+        raise ValueError(f"{who}: tile_merge={tile_merge!r} needs a soft method, nms=\"linear\" or nms=\"gaussian\" (with nms=\"hard\" use "
+                         f"tile_merge=\"agnostic\" or \"per_class\")")
 
 
 def check_tile_merge(who, tiles, class_aware, tile_merge):
     """the one rule of the `tile_merge` keyword, for the detectors and the functions in front of them: "agnostic" (the default,
-    mdcv_detect_merge_tiles) or "per_class" (mdcv_detect_merge_tiles_mc), which belongs to a tiled, class-aware detector"""
+    mdcv_detect_merge_tiles), "per_class" (mdcv_detect_merge_tiles_mc), which belongs to a tiled, class-aware detector, or the soft merges
+    of a tiled detector with a soft `nms` (mdcv_detect_merge_tiles_soft): "soft", and "soft_per_class" for a class-aware one"""
     if tile_merge not in TILE_MERGES:
         raise ValueError(f"{who}: tile_merge must be one of {TILE_MERGES}, got {tile_merge!r}")
-    if tile_merge == "per_class" and not tiles:
-        raise ValueError(f"{who}: tile_merge=\"per_class\" is for tiled detection (tiles=True) only")
-    if tile_merge == "per_class" and not class_aware:
-        raise ValueError(f"{who}: tile_merge=\"per_class\" needs class_aware=True (the tiles' detections carry no per-class NMS otherwise)")
-    if tiles and class_aware and tile_merge != "per_class":
+    if tile_merge != "agnostic" and not tiles:
+        raise ValueError(f"{who}: tile_merge=\"{tile_merge}\" is for tiled detection (tiles=True) only")
+    if tile_merge in ("per_class", "soft_per_class") and not class_aware:
+        raise ValueError(f"{who}: tile_merge=\"{tile_merge}\" needs class_aware=True (the tiles' detections carry no per-class NMS otherwise)")
+    if tile_merge == "soft" and class_aware:
+        raise ValueError(f"{who}: tile_merge=\"soft\" is class-agnostic and needs class_aware=False; pass tile_merge=\"soft_per_class\" with class_aware=True")
+    if tiles and class_aware and tile_merge not in ("per_class", "soft_per_class"):
         raise ValueError(TILED_CLASS_AWARE.format(who))
 
 TILE_DESC = 4                            # MDCV_TILE_DESC
@@ -251,7 +261,7 @@ class FrameDetector:
 
     def __init__(self, model, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
                  class_aware=False, nms="hard", sigma=0.5):
-        check_nms(type(self).__name__, isinstance(self, _Tiled), nms, sigma)
+        check_nms(type(self).__name__, False, nms, sigma)                    # the method itself; a tiled detector's rule: _init_tiles
         self.nms, self.sigma = nms, float(sigma)
         conf, nms, _ = model.get_threshs()
         self.model = model
@@ -544,10 +554,15 @@ class _Tiled:
     `detect_postprocess` in chunks of `tile_batch` tiles, ONE merge launch -- no count is read by the host.
     class_aware=True with tile_merge="per_class" (DESIGN.md §35): `detect_postprocess(class_aware=True)` per chunk and
     mdcv_detect_merge_tiles_mc (csrc/detect_tiles_mc.hip), which removes duplicates -- the seam rule included -- inside a class only and
-    writes the classes straight into the batch's cls table."""
+    writes the classes straight into the batch's cls table.
+    nms="linear" / "gaussian" with tile_merge="soft" (class_aware=False) or "soft_per_class" (class_aware=True): every
+    chunk runs `detect_postprocess(nms=, sigma=)` and the join is mdcv_detect_merge_tiles_soft (csrc/detect_tiles_soft.hip): boxes of
+    DIFFERENT tiles decay each other's scores instead of removing each other, the seam rule stays hard, the scan ends at conf_thres and
+    `prob` is the score at emission."""
 
     def _init_tiles(self, scale, tile_batch, contain_thres, class_aware=False, tile_merge="agnostic"):
         check_tile_merge(type(self).__name__, True, class_aware, tile_merge)
+        check_nms(type(self).__name__, True, self.nms, self.sigma, tile_merge)
         self.tile_merge = tile_merge
         self.class_aware = bool(class_aware)
         if not callable(scale):
@@ -565,13 +580,15 @@ class _Tiled:
         return [float(self.scale(w, h)) for w, h in sizes]
 
     def _batch_boxes(self, plan, dbuf, host, pool, st):
-        per_class = self.tile_merge == "per_class"
-        L = _lib.mctiles_lib() if per_class else _lib.lib()
+        soft = self.tile_merge in SOFT_TILE_MERGES
+        per_class = self.tile_merge in ("per_class", "soft_per_class")
+        L = _lib.softtiles_lib() if soft else _lib.mctiles_lib() if per_class else _lib.lib()
         B, K, NT = plan.B, plan.K, plan.NT
         imgs = I.launch_batch(dbuf, host, plan.layout, 1 if self.bw else 3, self.height, self.width, st, pool)      # [NT,C,H,W]
         self.model.eval()
         dets = [detect_postprocess(self.model(imgs[at:at + self.tile_batch]), None, self.conf_thres, self.nms_thres, 0.5, self.width,
-                                   self.height, self.top_k, class_aware=per_class) for at in range(0, NT, self.tile_batch)]
+                                   self.height, self.top_k, class_aware=per_class, nms=self.nms, sigma=self.sigma)      # "hard" unless soft
+                for at in range(0, NT, self.tile_batch)]
         one = len(dets) == 1
         tboxes = dets[0].boxes if one else torch.cat([d.boxes for d in dets])
         tprob = dets[0].prob if one else torch.cat([d.prob for d in dets])
@@ -581,8 +598,15 @@ class _Tiled:
         prob = torch.empty(B, K, dtype=torch.float32, device=dev)
         src = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
         count = torch.empty(B, dtype=torch.int32, device=dev)
-        if per_class:
-            tcls = dets[0].cls if one else torch.cat([d.cls for d in dets])
+        tcls = (dets[0].cls if one else torch.cat([d.cls for d in dets])) if per_class else None
+        if soft:                                                             # the tiles' decayed scores decay on across tiles; ends at conf_thres
+            L.check(L.detect_merge_tiles_soft(tboxes.data_ptr(), tprob.data_ptr(), tcls.data_ptr() if per_class else None, tcount.data_ptr(),
+                                              host.ctypes.data + plan.tile_off, dbuf.data_ptr() + plan.tile_off, NT, K, B, self.nms_thres,
+                                              self.contain_thres, K, boxes.data_ptr(), prob.data_ptr(),
+                                              dbuf.data_ptr() + plan.cls_off if per_class else None, src.data_ptr(), count.data_ptr(),
+                                              _lib.NMS_METHODS[self.nms], self.sigma, self.conf_thres, int(per_class), st.cuda_stream),
+                    "detect_merge_tiles_soft")
+        elif per_class:
             L.check(L.detect_merge_tiles_mc(tboxes.data_ptr(), tprob.data_ptr(), tcls.data_ptr(), tcount.data_ptr(),
                                             host.ctypes.data + plan.tile_off, dbuf.data_ptr() + plan.tile_off, NT, K, B, self.nms_thres,
                                             self.contain_thres, K, boxes.data_ptr(), prob.data_ptr(), dbuf.data_ptr() + plan.cls_off,
@@ -603,7 +627,8 @@ class TiledFrameDetector(_Tiled, FrameDetector):
     `nms_thres`; `contain_thres` (None: off) also removes a box of one tile that lies to more than that fraction of the smaller area
     inside a more confident box of another tile -- the part of a cone a tile edge cut off.  Yields `TiledFrameDetections` (boxes in
     frame pixels: merged box / scale).  ONE host synchronisation per batch.  `tile_merge`: "agnostic" (one NMS over all of a frame's
-    candidates) or, with class_aware=True, "per_class" (class scores, and both rules of the merge inside a class only; `cls` is filled)."""
+    candidates) or, with class_aware=True, "per_class" (class scores, and both rules of the merge inside a class only; `cls` is filled);
+    with nms="linear" / "gaussian": "soft" or, with class_aware=True, "soft_per_class" (Soft-NMS in the tiles and across them)."""
 
     _result_type = TiledFrameDetections
 
@@ -654,7 +679,7 @@ def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, cont
     are built on the model's device, so the two must be the same GPU.  None: the model's device.  `tiles`: a TiledFrameDetector at
     `scale` with `contain_thres` and `tile_merge`; otherwise the first two are not looked at and tile_merge must be its default."""
     check_tile_merge("detect", tiles, kw.get("class_aware", False), tile_merge)
-    check_nms("detect", tiles, kw.get("nms", "hard"), kw.get("sigma", 0.5))
+    check_nms("detect", tiles, kw.get("nms", "hard"), kw.get("sigma", 0.5), tile_merge)
     if device is not None:
         want, have = torch.device(device), next(model.parameters()).device
         if want.type != "cuda":
@@ -674,9 +699,10 @@ def single_img_detect(target_path, output_path, mode, model, device, conf_thres,
     saved unannotated.  `device` must be the GPU the model is on (or None).  Each call builds its own detector: for many files use `detect`
     on their directory.  Keyword-only `tiles=True`: tile-and-scale inference at `scale` (TiledFrameDetector), the counterpart of training
     with ts=True; the defaults are the reference's whole-frame pad and resize.  `class_aware`: FrameDetector's; with tiles it needs
-    `tile_merge="per_class"` (TiledFrameDetector's).  `nms`, `sigma`: FrameDetector's; a soft method is for tiles=False."""
+    `tile_merge="per_class"` (TiledFrameDetector's).  `nms`, `sigma`: FrameDetector's; with tiles a soft method needs
+    `tile_merge="soft"` (class_aware=True: "soft_per_class")."""
     check_tile_merge("single_img_detect", tiles, class_aware, tile_merge)
-    check_nms("single_img_detect", tiles, nms, sigma)
+    check_nms("single_img_detect", tiles, nms, sigma, tile_merge)
     frame = _open_rgb(target_path)
     det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=1, class_aware=class_aware,
                     nms=nms, sigma=sigma)
@@ -693,7 +719,7 @@ def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch
     Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead.
     Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`, `tile_merge`, `nms`, `sigma`: as in `single_img_detect`."""
     check_tile_merge("detect", tiles, class_aware, tile_merge)
-    check_nms("detect", tiles, nms, sigma)
+    check_nms("detect", tiles, nms, sigma, tile_merge)
     ext = os.path.splitext(target_path)[-1].lower()
     if os.path.isdir(target_path):
         names = sorted(f for f in os.listdir(target_path)

@@ -348,10 +348,12 @@ def main(argv=None):
     p.add_argument('--precision', type=str, default=None, choices=["bf16", "fp32"], help='precision of the network (default: the model\'s)')
     p.add_argument('--class_aware', action='store_true',
                    help='class scores, per-class NMS and class-restricted matching (with --tiles: together with --tile_merge per_class)')
-    p.add_argument('--tile_merge', type=str, default="agnostic", choices=["agnostic", "per_class"],
-                   help='frame mode with --tiles: the cross-tile merge; per_class (needs --class_aware) removes duplicates inside a class only')
+    p.add_argument('--tile_merge', type=str, default="agnostic", choices=list(_lib.TILE_MERGES),
+                   help='frame mode with --tiles: the cross-tile merge; per_class (needs --class_aware) removes duplicates inside a class only; '
+                        'soft / soft_per_class (with --class_aware) go with --nms linear or gaussian: scores decay across tiles too')
     p.add_argument('--nms', type=str, default="hard", choices=["hard", "linear", "gaussian"],
-                   help='the suppression rule: greedy hard NMS, or Soft-NMS with a linear or Gaussian score decay (not with --tiles)')
+                   help='the suppression rule: greedy hard NMS, or Soft-NMS with a linear or Gaussian score decay '
+                        '(with --tiles: together with --tile_merge soft / soft_per_class)')
     p.add_argument('--nms_sigma', type=float, default=0.5, help='--nms gaussian: the decay is exp(-IoU^2 / sigma)')
     a = p.parse_args(argv)
     device = torch.device("cuda", torch.cuda.current_device())
