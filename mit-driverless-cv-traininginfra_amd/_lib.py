@@ -3,8 +3,8 @@ DESIGN §29; `kptaug_lib()`), of libmdcv_cls.so (the opt-in class l
 libmdcv_box.so (its opt-in box loss: `box_lib()`), of libmdcv_ign.so (the opt-in prediction-IoU ignore rule of its
 no-object term: `ign_lib()`), of libmdcv_mcdet.so (the opt-in class-aware detection post-processing: `mcdet_lib()`,
 DESIGN §34), of libmdcv_mctiles.so (the opt-in class-aware cross-tile merge: `mctiles_lib()`), of libmdcv_softnms.so
-(the opt-in Soft-NMS post-processing: `softnms_lib()`) and of libmdcv_softtiles.so (the opt-in soft cross-tile merge:
-`softtiles_lib()`).
+(the opt-in Soft-NMS post-processing: `softnms_lib()`), of libmdcv_softtiles.so (the opt-in soft cross-tile merge:
+`softtiles_lib()`) and of libmdcv_pnp.so (the opt-in cone pose solver: `pnp_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -51,6 +51,8 @@ SOFTNMS_HEADER = os.path.join(ROOT, "include", "mdcv_softnms.h")
 SOFTNMS_LIB_PATH = os.path.join(_HERE, "libmdcv_softnms.so")
 SOFTTILES_HEADER = os.path.join(ROOT, "include", "mdcv_softtiles.h")
 SOFTTILES_LIB_PATH = os.path.join(_HERE, "libmdcv_softtiles.so")
+PNP_HEADER = os.path.join(ROOT, "include", "mdcv_pnp.h")
+PNP_LIB_PATH = os.path.join(_HERE, "libmdcv_pnp.so")
 NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}   # include/mdcv_softnms.h MDCV_SNMS_HARD / _LINEAR / _GAUSSIAN
 
 F32, BF16 = 0, 1
@@ -242,6 +244,18 @@ def softtiles_lib():
     if _softtiles is None:
         _softtiles = _Lib(SOFTTILES_LIB_PATH, SOFTTILES_HEADER, "libmdcv_softtiles")
     return _softtiles
+
+
+_pnp = None
+
+
+def pnp_lib():
+    """libmdcv_pnp.so behind include/mdcv_pnp.h: the same binding and `check`, loaded on first use -- by
+    mdcv.rektnet.pose.solve_cone_pnp only"""
+    global _pnp
+    if _pnp is None:
+        _pnp = _Lib(PNP_LIB_PATH, PNP_HEADER, "libmdcv_pnp")
+    return _pnp
 
 
 def nms_method(who, name, sigma=0.5):

@@ -81,7 +81,12 @@ class KeypointDetector:
     """`KeypointDetector(model, img_size=80).detect_crops(crops)`: see the module docstring.  `model`: a KeypointNet on a GPU, built for
     `img_size`; `colours`: seven RGB triples, key point 0 to 6 (default: the reference's)."""
 
-    def __init__(self, model, img_size=80, batch_size=16, colours=KPT_COLOURS_RGB):
+    def __init__(self, model, img_size=80, batch_size=16, colours=KPT_COLOURS_RGB, camera=None, cone_model=None, pnp_iters=30):
+        from . import pose as P
+        self.camera = None if camera is None else P.check_camera(camera, frames=1)       # the crop is the camera's whole image (DESIGN.md §38)
+        self.cone_model, self.pnp_iters, self._pose_dev = P.check_model(cone_model), int(pnp_iters), None
+        if self.pnp_iters < 1:
+            raise ValueError(f"KeypointDetector: pnp_iters must be at least 1, got {pnp_iters!r}")
         self.model, self.size, self.batch_size = model, int(img_size), int(batch_size)
         if not MIN_SIZE <= self.size <= MAX_SIZE:
             raise ValueError(f"KeypointDetector: img_size {img_size} outside {MIN_SIZE}..{MAX_SIZE}")
@@ -121,6 +126,14 @@ class KeypointDetector:
                 raise _lib.MdcvError(f"KeypointDetector: heat-maps of shape {tuple(hm.shape)}, expected {(B, NUM_KPT, S, S)}")
             hm = hm.contiguous()
             dbuf[plan.pts_off:plan.pts_off + B * NUM_KPT * 8].view(torch.float32).copy_(pts.reshape(-1))
+            poses = None
+            if self.camera is not None:                          # on the same stream, on the tables where they lie; ONE MORE host read behind the copy back
+                from .pose import solve_cone_pnp
+                if self._pose_dev is None:
+                    self._pose_dev = [torch.from_numpy(a).pin_memory().to(dev, non_blocking=True) for a in (self.camera, self.cone_model)]
+                poses = solve_cone_pnp(dbuf[plan.pts_off:plan.pts_off + B * NUM_KPT * 8].view(torch.float32).view(B, NUM_KPT, 2), self._pose_dev[0],
+                                       self._pose_dev[1], dbuf[plan.window_off:plan.window_off + B * 16].view(torch.int32).view(B, 4),
+                                       max_iters=self.pnp_iters)
             L.check(L.kpt_draw_points(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.pts_off, base + plan.window_off,
                                       base + plan.owner_off, B, self.colours.ctypes.data, base + plan.centers_off, base + plan.skip_off,
                                       st.cuda_stream), "kpt_draw_points")
@@ -131,12 +144,17 @@ class KeypointDetector:
         kpts = table(plan.pts_off, B * NUM_KPT * 8, np.float32, (B, NUM_KPT, 2)).copy()       # the pinned buffer is the next batch's
         centers = table(plan.centers_off, B * NUM_KPT * 8, np.int32, (B, NUM_KPT, 2)).copy()
         mosaic = table(plan.mosaic_off, B * NUM_KPT * S * S, np.uint8, (B, NUM_KPT * S, S)).copy()
+        t = None if poses is None else poses.t.cpu().numpy()
         for b, (off, (w, h)) in enumerate(zip(plan.offsets, plan.sizes)):
-            yield kpts[b], centers[b], table(plan.pool_off + off, 3 * w * h, np.uint8, (h, w, 3)).copy(), mosaic[b]
+            out = kpts[b], centers[b], table(plan.pool_off + off, 3 * w * h, np.uint8, (h, w, 3)).copy(), mosaic[b]
+            yield out if t is None else out + (t[b],)
 
     def detect_crops(self, crops):
         """crops: any iterable of (H, W, 3) uint8 RGB arrays (sizes may differ) -> yields, per crop and in order, (keypoints float32 [7,2]
-        normalised x, y; centers int32 [7,2] as drawn, (-1, -1) for a point not drawn; annotated (H, W, 3) uint8; mosaic (7*S, S) uint8)"""
+        normalised x, y; centers int32 [7,2] as drawn, (-1, -1) for a point not drawn; annotated (H, W, 3) uint8; mosaic (7*S, S) uint8),
+        and with a `camera` a fifth item: the cone's position float64 [3], metres in the camera frame (NaN for a degenerate cone).  The
+        positions are read with a second device-to-host copy per batch (this path prints them; the frame detectors' poses ride in their
+        one copy back)"""
         _lib.require_gpu()
         it, first = iter(crops), 0
         while True:
@@ -158,22 +176,43 @@ def load_model(model, img_size=80, device="cuda"):
     return net.to(device).eval()
 
 
-def detect(model, img, img_size=80, output="outputs/visualization/", flip=False, rotate=False, batch_size=16, ext=".jpg"):
+def detect(model, img, img_size=80, output="outputs/visualization/", flip=False, rotate=False, batch_size=16, ext=".jpg", camera=None):
     """RektNet/detect.py:13-55 (`main`).  `img`: an image file, or a directory whose image files (.jpg / .jpeg / .png / .tif), sorted by
     name, are run in batches of `batch_size`.  Per file it writes `output + <name> + "_hm" + ext` (the heat-map mosaic) and
     `output + <name> + "_inference" + ext` (the crop with its key points), `<name>` as detect.py:25 builds it and `output` joined as the
     reference joins it (plain concatenation for `_hm`; the directory must exist) -> the list of (inference path, hm path).  `flip` and
-    `rotate` are accepted and ignored, as in the reference.  `ext`: ".png" for a lossless copy of the arrays."""
+    `rotate` are accepted and ignored, as in the reference.  `ext`: ".png" for a lossless copy of the arrays.  `camera`: (fx, fy, cx, cy) of
+    the image the file holds -> each crop's key points and the cone's position in the camera frame are printed."""
     if os.path.isdir(img):
         files = sorted(os.path.join(img, f) for f in os.listdir(img)
                        if os.path.splitext(f)[-1].lower() in IMG_FORMATS and os.path.isfile(os.path.join(img, f)))
     else:
         files = [img]
-    det = KeypointDetector(load_model(model, img_size), img_size=img_size, batch_size=batch_size)
+    det = KeypointDetector(load_model(model, img_size), img_size=img_size, batch_size=batch_size, camera=camera)
     paths = []
-    for f, (_kp, _c, annotated, mosaic) in zip(files, det.detect_crops(_open_rgb(f) for f in files)):
+    for f, (kp, _c, annotated, mosaic, *pos) in zip(files, det.detect_crops(_open_rgb(f) for f in files)):
         name = image_name(f)
+        if pos:
+            print(f"{name}: key points {np.round(kp, 4).tolist()} position (m) {pos[0].tolist()}")
         hm_path = _save(mosaic, output + name + "_hm" + ext)
         print(f"please check the output image here: {hm_path}")
         paths.append((_save(annotated, os.path.join(output, name + "_inference" + ext)), hm_path))
     return paths
+
+
+def main(argv=None):
+    """`python -m mdcv.rektnet.detect --model m.pt --img crop.jpg [--camera fx,fy,cx,cy]`: RektNet/detect.py's command line"""
+    import argparse
+    from .pose import parse_camera
+    ap = argparse.ArgumentParser(description="key points of cone crops, drawn on the device")
+    ap.add_argument("--model", required=True)
+    ap.add_argument("--img", required=True)
+    ap.add_argument("--img_size", type=int, default=80)
+    ap.add_argument("--output", default="outputs/visualization/")
+    ap.add_argument("--camera", type=parse_camera, default=None, help="fx,fy,cx,cy in pixels: also print each cone's position")
+    a = ap.parse_args(argv)
+    return detect(a.model, a.img, a.img_size, a.output, camera=a.camera)
+
+
+if __name__ == "__main__":
+    main()

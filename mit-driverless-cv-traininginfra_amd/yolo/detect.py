@@ -428,6 +428,13 @@ def _append_cone_tables(plan, max_cones):
     plan.nbytes = _align(plan.kskip_off + plan.B * 4)
 
 
+def _append_pose_tables(plan):
+    """behind everything else, only when the detector has a camera: [pose cap,16 f64] [info cap,4 i32] of mdcv_cone_pnp"""
+    plan.pose_off = plan.nbytes
+    plan.info_off = plan.pose_off + plan.cap * 128
+    plan.nbytes = _align(plan.info_off + plan.cap * 16)
+
+
 class TiledConeBatchPlan(TiledBatchPlan):
     """TiledBatchPlan with ConeBatchPlan's tables behind it"""
 
@@ -452,9 +459,12 @@ class FrameCones(FrameDetections):
     """One frame's result: FrameDetections' fields, and per box keypoints float32 [n,7,2] (x, y normalised in the crop; NaN for a box
     without a crop), keypoints_frame int32 [n,7,2] (the disc centres as drawn, in frame pixels; (-1, -1) for a box without a crop or a
     point that was skipped), has_crop bool [n], skipped_points (key points of this frame not drawn), and crops (float32 [c,3,S,S], the
-    KeypointNet inputs of the boxes with a crop in box order; None unless asked for)."""
+    KeypointNet inputs of the boxes with a crop in box order; None unless asked for), windows int32 [n,4] (x0, y0, w, h of each crop in
+    frame pixels, the table the key points are normalised in; zeros for a box without a crop).
+    With a `camera` (all None without one): position float64 [n,3] (metres, camera frame), rotation float64 [n,3,3],
+    reproj_rms float64 [n] (pixels) -- NaN for a box without a crop or a degenerate cone --, pose_ok bool [n]."""
 
-    __slots__ = ("keypoints", "keypoints_frame", "has_crop", "skipped_points", "crops")
+    __slots__ = ("keypoints", "keypoints_frame", "has_crop", "skipped_points", "crops", "windows", "position", "rotation", "reproj_rms", "pose_ok")
 
 
 class FrameConeDetector(FrameDetector):
@@ -470,8 +480,10 @@ class FrameConeDetector(FrameDetector):
     `detect_frames(..., return_crops=True)` also copies the crops back (a third synchronisation; tests and debugging)."""
 
     def __init__(self, model, keypoint_net, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, class_aware=False, nms="hard", sigma=0.5):
+                 max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, class_aware=False, nms="hard", sigma=0.5, camera=None, cone_model=None,
+                 pnp_iters=30):
         super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, class_aware, nms, sigma)
+        self._init_pose(camera, cone_model, pnp_iters)
         self.keypoint_net = keypoint_net
         self.max_cones, self.bucket = int(max_cones), int(bucket)
         if self.max_cones < 1 or self.bucket < 1:
@@ -487,8 +499,39 @@ class FrameConeDetector(FrameDetector):
 
     _result_type = FrameCones
 
+    # -- cone poses: `camera` = one (fx, fy, cx, cy) or one per frame of the call; mdcv_cone_pnp then runs on the batch's
+    #    stream behind the key-point forward on the pts / window / owner tables where they lie, and its two tables ride in the one copy back
+    def _init_pose(self, camera, cone_model, pnp_iters):
+        self.camera = self._pose_dev = None
+        if camera is None:
+            return
+        from ..rektnet import pose as P
+        self.camera, self.cone_model, self.pnp_iters = P.check_camera(camera), P.check_model(cone_model), int(pnp_iters)
+        if self.pnp_iters < 1:
+            raise ValueError(f"{type(self).__name__}: pnp_iters must be at least 1, got {pnp_iters!r}")
+
+    def _with_pose(self, plan, first):
+        if self.camera is not None:
+            if len(self.camera) > 1 and first + plan.B > len(self.camera):
+                raise ValueError(f"{type(self).__name__}: {len(self.camera)} cameras but the call has more frames; pass one (fx, fy, cx, cy) "
+                                 f"for all frames or exactly one per frame")
+            plan.first = first
+            _append_pose_tables(plan)
+        return plan
+
+    def _solve_poses(self, plan, base, M, st):
+        if self._pose_dev is None:                               # the two small tables, uploaded once from pinned memory: no synchronisation
+            host = [torch.from_numpy(a).pin_memory() for a in (self.camera, self.cone_model)]
+            self._pose_dev = [h.to(self.device, non_blocking=True) for h in host] + host
+        cam, mod = self._pose_dev[:2]
+        one = len(self.camera) == 1
+        L = _lib.pnp_lib()
+        L.check(L.cone_pnp(base + plan.pts_off, base + plan.window_off, base + plan.owner_off, cam.data_ptr() + (0 if one else plan.first * 32),
+                           1 if one else plan.B, mod.data_ptr(), M, self.pnp_iters, base + plan.pose_off, base + plan.info_off, st.cuda_stream),
+                "cone_pnp")
+
     def _plan(self, sizes, first):
-        return ConeBatchPlan(sizes, self.width, self.height, self.top_k, self.max_cones, self.class_aware)
+        return self._with_pose(ConeBatchPlan(sizes, self.width, self.height, self.top_k, self.max_cones, self.class_aware), first)
 
     def _annotate(self, plan, slot, dbuf, host, boxes, count, st):
         L = _lib.lib()
@@ -514,6 +557,8 @@ class FrameConeDetector(FrameDetector):
             self.keypoint_net.eval()
             _hm, pts = self.keypoint_net(crops[:rows])
             dbuf[plan.pts_off:plan.pts_off + M * NUM_KPT * 8].view(torch.float32).copy_(pts[:M].reshape(-1))
+            if self.camera is not None:
+                self._solve_poses(plan, base, M, st)
         self._draw_boxes(plan, dbuf, host, boxes, count, st)
         L.check(L.kpt_draw_points(desc_h, desc_d, B, base + plan.pool_off, plan.pool_bytes, base + plan.pts_off, base + plan.window_off,
                                   base + plan.owner_off, M, self.colours.ctypes.data, base + plan.centers_off, base + plan.kskip_off,
@@ -527,17 +572,44 @@ class FrameConeDetector(FrameDetector):
         kpts = table(plan.pts_off, M * NUM_KPT * 8, np.float32, (M, NUM_KPT, 2))
         centers = table(plan.centers_off, M * NUM_KPT * 8, np.int32, (M, NUM_KPT, 2))
         kskip = table(plan.kskip_off, plan.B * 4, np.int32, (plan.B,))
+        window = table(plan.window_off, M * 16, np.int32, (M, 4))
+        posed = self.camera is not None
+        pose = table(plan.pose_off, M * 128, np.float64, (M, 16)) if posed else None
+        info = table(plan.info_off, M * 16, np.int32, (M, 4)) if posed else None
 
         def add(r, b, n):
             r.keypoints, r.keypoints_frame, r.has_crop, rows = scatter_cones(owner, kpts, centers, b, n)
             r.skipped_points = int(kskip[b])
             r.crops = crops_host[rows] if crops_host is not None else None
+            r.windows = np.zeros((n, 4), np.int32)
+            r.windows[owner[rows, 1]] = window[rows]
+            r.position = r.rotation = r.reproj_rms = r.pose_ok = None
+            if posed:
+                full = np.full((n, 16), np.nan)
+                full[owner[rows, 1]] = pose[rows]
+                r.position, r.rotation, r.reproj_rms = full[:, :3].copy(), full[:, 3:12].reshape(n, 3, 3).copy(), full[:, 12].copy()
+                r.pose_ok = np.zeros(n, bool)
+                r.pose_ok[owner[rows, 1]] = (info[rows, 0] & 31) == 0          # no MDCV_PNP_* degenerate bit
         return add
 
     def detect_frames(self, frames, keep_on_device=False, return_crops=False):
         """as FrameDetector.detect_frames -> yields one `FrameCones` per frame, in order"""
         self._return_crops = bool(return_crops)
-        return super().detect_frames(frames, keep_on_device)
+        if self.camera is not None and len(self.camera) > 1 and hasattr(frames, "__len__") and len(frames) != len(self.camera):
+            raise ValueError(f"{type(self).__name__}: {len(self.camera)} cameras but {len(frames)} frames; pass one (fx, fy, cx, cy) for all "
+                             f"frames or exactly one per frame")
+        results = super().detect_frames(frames, keep_on_device)      # an iterable without a length: too many frames raise at the batch
+        return results if self.camera is None or len(self.camera) == 1 else self._counted(results)
+
+    def _counted(self, results):
+        """too FEW frames for the cameras can only be known at exhaustion: the ValueError comes behind the last result"""
+        n = 0
+        for r in results:
+            n += 1
+            yield r
+        if n != len(self.camera):
+            raise ValueError(f"{type(self).__name__}: {len(self.camera)} cameras but the call had {n} frames; pass one (fx, fy, cx, cy) for all "
+                             f"frames or exactly one per frame")
 
 
 # ------------------------------------------------------------------------------------------------- tile-and-scale inference (DESIGN.md §22)
@@ -649,13 +721,14 @@ class TiledFrameConeDetector(_Tiled, FrameConeDetector):
 
     def __init__(self, model, keypoint_net, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0),
                  batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None, class_aware=False,
-                 tile_merge="agnostic", nms="hard", sigma=0.5):
+                 tile_merge="agnostic", nms="hard", sigma=0.5, camera=None, cone_model=None, pnp_iters=30):
         super().__init__(model, keypoint_net, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, max_cones, bucket, colours,
-                         nms=nms, sigma=sigma)
+                         nms=nms, sigma=sigma, camera=camera, cone_model=cone_model, pnp_iters=pnp_iters)
         self._init_tiles(scale, tile_batch, contain_thres, class_aware, tile_merge)
 
     def _plan(self, sizes, first):
-        return TiledConeBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), self.max_cones, first, self.class_aware)
+        return self._with_pose(TiledConeBatchPlan(sizes, self.width, self.height, self.top_k, self._scales(sizes), self.max_cones, first,
+                                                  self.class_aware), first)
 
 
 # --------------------------------------------------------------------------------------------- the reference's two functions (detect.py)
