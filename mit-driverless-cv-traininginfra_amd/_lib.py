@@ -4,7 +4,8 @@ libmdcv_box.so (its opt-in box loss: `box_lib()`), of libmdcv_ign.s
 no-object term: `ign_lib()`), of libmdcv_mcdet.so (the opt-in class-aware detection post-processing: `mcdet_lib()`,
 DESIGN §34), of libmdcv_mctiles.so (the opt-in class-aware cross-tile merge: `mctiles_lib()`), of libmdcv_softnms.so
 (the opt-in Soft-NMS post-processing: `softnms_lib()`), of libmdcv_softtiles.so (the opt-in soft cross-tile merge:
-`softtiles_lib()`) and of libmdcv_pnp.so (the opt-in cone pose solver: `pnp_lib()`).
+`softtiles_lib()`), of libmdcv_pnp.so (the opt-in cone pose solver: `pnp_lib()`) and of libmdcv_track.so (the
+opt-in tracker: `track_lib()`).
 
 Prototypes are parsed from ``include/mdcv_hip.h`` (``include/mdcv_aug.h``) so the header is the single source of truth for the C ABI.
 There is NO CPU fallback: if the shared library is missing, or an entry point is asked to run without a GPU, this
@@ -53,6 +54,8 @@ SOFTTILES_HEADER = os.path.join(ROOT, "include", "mdcv_softtiles.h")
 SOFTTILES_LIB_PATH = os.path.join(_HERE, "libmdcv_softtiles.so")
 PNP_HEADER = os.path.join(ROOT, "include", "mdcv_pnp.h")
 PNP_LIB_PATH = os.path.join(_HERE, "libmdcv_pnp.so")
+TRACK_HEADER = os.path.join(ROOT, "include", "mdcv_track.h")
+TRACK_LIB_PATH = os.path.join(_HERE, "libmdcv_track.so")
 NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}   # include/mdcv_softnms.h MDCV_SNMS_HARD / _LINEAR / _GAUSSIAN
 
 F32, BF16 = 0, 1
@@ -256,6 +259,18 @@ def pnp_lib():
     if _pnp is None:
         _pnp = _Lib(PNP_LIB_PATH, PNP_HEADER, "libmdcv_pnp")
     return _pnp
+
+
+_track = None
+
+
+def track_lib():
+    """libmdcv_track.so behind include/mdcv_track.h: the same binding and `check`, loaded on first use -- by
+    mdcv.yolo.track.track_boxes and a detector's first batch with `track=` only"""
+    global _track
+    if _track is None:
+        _track = _Lib(TRACK_LIB_PATH, TRACK_HEADER, "libmdcv_track")
+    return _track
 
 
 def nms_method(who, name, sigma=0.5):

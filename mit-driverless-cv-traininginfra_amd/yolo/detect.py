@@ -42,6 +42,7 @@ from .. import _lib
 from ..data import images as I
 from ..data import staging
 from .postprocess import detect_postprocess, L_MAX_TOPK
+from .track import check_track
 
 DETECT_DESC = 6                          # MDCV_DETECT_DESC
 IMG_FORMATS = (".jpg", ".jpeg", ".png", ".tif")         # detect.py:122-123
@@ -75,10 +76,12 @@ class BatchPlan:
     descriptors] [pool: the whole frames] [frame_boxes B,K,4 f64] [rects B,K,4 i32] [prob B,K f32] [count B i32] [skipped B i32];
     the pinned input is everything up to the end of the pool, the copy back is everything from the pool (or from the tables) on.
     Subclasses choose the resize samples (`_samples`) and may put input tables behind the detect descriptors (`_tables`).
-    class_aware: [cls B,K i32] behind `skipped`; without it no byte of the layout moves."""
+    class_aware: [cls B,K i32] behind `skipped`; without it no byte of the layout moves.  A detector with `track` appends [track_id B,K i32]
+    [track flags B,K u8] behind everything else (`_append_track_tables`)"""
 
     src_off = None                           # tiled plans: [src B,K,2 i32] behind the tables
     cls_off = None                           # class-aware plans: [cls B,K i32]
+    tid_off = None                           # tracking plans: [track_id B,K i32] [flags B,K u8]
 
     def __init__(self, sizes, width, height, K, class_aware=False):
         B = len(sizes)
@@ -218,6 +221,13 @@ class TiledBatchPlan(BatchPlan):
         host[self.tile_off:self.tile_off + self.tile_table.nbytes].view(np.int32)[:] = self.tile_table.reshape(-1)
 
 
+def _append_track_tables(plan):
+    """behind everything else, only when the detector tracks: [track_id B,K i32] [flags B,K u8] of mdcv_track_frames"""
+    plan.tid_off = plan.nbytes
+    plan.tflag_off = plan.tid_off + plan.B * plan.K * 4
+    plan.nbytes = _align(plan.tflag_off + plan.B * plan.K)
+
+
 def _check_frame(f, i):
     f = np.asarray(f)
     if f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8 or f.shape[0] < 1 or f.shape[1] < 1:
@@ -228,12 +238,15 @@ def _check_frame(f, i):
 class FrameDetections:
     """One frame's result.  boxes float64 [n,4] (x0, y0, x1, y1 in frame coordinates, most confident first), prob float32 [n], rects int32
     [n,4] (the truncated boxes as drawn; (0, 0, -1, -1) for a skipped one), skipped (boxes not drawn), annotated (H, W, 3) uint8 -- a
-    NumPy array, or a device tensor with `keep_on_device`, cls int32 [n] (the class of each box; None unless the detector is class-aware)."""
+    NumPy array, or a device tensor with `keep_on_device`, cls int32 [n] (the class of each box; None unless the detector is class-aware).
+    With `track` (both None without): track_id int32 [n] (the id of the box's track in this call's sequence, -1 for a box
+    without one), confirmed bool [n]."""
 
-    __slots__ = ("boxes", "prob", "rects", "skipped", "annotated", "cls")
+    __slots__ = ("boxes", "prob", "rects", "skipped", "annotated", "cls", "track_id", "confirmed")
 
     def __init__(self, boxes, prob, rects, skipped, annotated, cls=None):
         self.boxes, self.prob, self.rects, self.skipped, self.annotated, self.cls = boxes, prob, rects, skipped, annotated, cls
+        self.track_id = self.confirmed = None
 
 
 class TiledFrameDetections(FrameDetections):
@@ -255,12 +268,14 @@ class FrameDetector:
     `_result_type`; FrameConeDetector also `_annotate` and `_extras`; everything else -- staging, the copy back, the final synchronisation -- is shared.
     class_aware=True: `detect_postprocess(class_aware=True)` -- class scores, per-class NMS, `prob` the class score; the
     results then carry `cls`.  nms="linear" / "gaussian" with `sigma`: `detect_postprocess`'s Soft-NMS, `prob`
-    the decayed score, the scan ending at conf_thres."""
+    the decayed score, the scan ending at conf_thres.  track=True / a `TrackConfig` (mdcv/yolo/track.py): every
+    `detect_frames` call is one sequence with fresh state and ids from 0; mdcv_track_frames runs on the batch's stream on the box, count
+    and -- class-aware -- class tables where they lie, and the results carry `track_id` and `confirmed`; max_boxes <= 256."""
 
     _result_type = FrameDetections
 
     def __init__(self, model, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 class_aware=False, nms="hard", sigma=0.5):
+                 class_aware=False, nms="hard", sigma=0.5, track=None):
         check_nms(type(self).__name__, False, nms, sigma)                    # the method itself; a tiled detector's rule: _init_tiles
         self.nms, self.sigma = nms, float(sigma)
         conf, nms, _ = model.get_threshs()
@@ -276,6 +291,7 @@ class FrameDetector:
         self.outline = tuple(int(c) for c in outline)
         if len(self.outline) != 3 or any(not 0 <= c <= 255 for c in self.outline):
             raise ValueError(f"FrameDetector: outline must be one RGB triple of bytes, got {outline!r}")
+        self.track = check_track(type(self).__name__, track, self.max_boxes)
         self.bw = bool(model.get_bw())
         self.width, self.height = (int(v) for v in model.img_size())
 
@@ -292,6 +308,8 @@ class FrameDetector:
         if not frames:
             return None
         plan = self._plan([(f.shape[1], f.shape[0]) for f in frames], first)
+        if self.track is not None:
+            _append_track_tables(plan)
         slot.pin_in = staging.pinned(slot.pin_in, plan.in_bytes)
         plan.pack(slot.pin_in.numpy(), frames)
         return plan, slot
@@ -327,8 +345,16 @@ class FrameDetector:
     def _extras(self, plan, table, annotated):
         return lambda r, b, n: None
 
+    # -- tracking: the batch's frames continue the call's one sequence; on the same stream, on the tables where they lie
+    def _track_batch(self, plan, state, dbuf, st):
+        from .track import launch
+        base, K = dbuf.data_ptr(), plan.K
+        gate = self.class_aware and plan.cls_off is not None
+        launch(self.track, state.data_ptr(), base + plan.fb_off, (0, K * 4), base + plan.count_off, (0, 1),
+               base + plan.cls_off if gate else None, (0, K), 1, plan.B, K, base + plan.tid_off, base + plan.tflag_off, st.cuda_stream)
+
     # -- device half: copy, boxes, draw, copy back, ONE synchronisation
-    def _run(self, plan, slot, keep_on_device):
+    def _run(self, plan, slot, keep_on_device, track_state=None):
         dev = self.device
         B, K = plan.B, plan.K
         with torch.cuda.device(dev), torch.no_grad():
@@ -342,6 +368,8 @@ class FrameDetector:
             dbuf[plan.count_off:plan.count_off + B * 4].view(torch.int32).copy_(count)
             if src is not None:
                 dbuf[plan.src_off:plan.src_off + B * K * 8].view(torch.int32).copy_(src.reshape(-1))
+            if plan.tid_off is not None:
+                self._track_batch(plan, track_state, dbuf, st)
             lo = plan.fb_off if keep_on_device else plan.pool_off
             slot.pin_out, table = staging.copy_back(dbuf, lo, slot.pin_out, st)       # the batch's one (or last) host synchronisation
             add = self._extras(plan, table, annotated)
@@ -351,6 +379,8 @@ class FrameDetector:
         cnt = table(plan.count_off, B * 4, np.int32, (B,))
         skipped = table(plan.skip_off, B * 4, np.int32, (B,))
         cls = table(plan.cls_off, B * K * 4, np.int32, (B, K)) if plan.cls_off is not None else None
+        tid = table(plan.tid_off, B * K * 4, np.int32, (B, K)) if plan.tid_off is not None else None
+        tflag = table(plan.tflag_off, B * K, np.uint8, (B, K)) if plan.tid_off is not None else None
         res = []
         for b, (off, (w, h)) in enumerate(zip(plan.offsets, plan.sizes)):
             n = min(int(cnt[b]), K)
@@ -362,6 +392,8 @@ class FrameDetector:
                                   None if cls is None else cls[b, :n].copy())
             if plan.src_off is not None:
                 r.src = table(plan.src_off, B * K * 8, np.int32, (B, K, 2))[b, :n].copy()
+            if tid is not None:
+                r.track_id, r.confirmed = tid[b, :n].copy(), (tflag[b, :n] & 1) != 0
             add(r, b, n)
             res.append(r)
         return res
@@ -372,6 +404,11 @@ class FrameDetector:
         _lib.require_gpu()
         it = iter(frames)
         slots = [_Slot(), _Slot()]                               # this generator's own: several may be alive on one detector
+        track_state = None                                       # with `track`: this call's sequence, a fresh (all-zero) state block
+        if self.track is not None:
+            from .track import STATE_BYTES
+            with torch.cuda.device(self.device):
+                track_state = torch.zeros(STATE_BYTES, dtype=torch.uint8, device=self.device)
         stager = ThreadPoolExecutor(1, thread_name_prefix="mdcv-detect-stage")
         try:
             n, first = 0, 0
@@ -383,7 +420,7 @@ class FrameDetector:
                 n += 1
                 first += staged[0].B
                 pending = stager.submit(self._stage, it, first, slots[n % 2])     # packed while the device works on this batch
-                yield from self._run(*staged, keep_on_device)
+                yield from self._run(*staged, keep_on_device, track_state)
         finally:
             stager.shutdown(wait=True, cancel_futures=True)
 
@@ -481,8 +518,8 @@ class FrameConeDetector(FrameDetector):
 
     def __init__(self, model, keypoint_net, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
                  max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, class_aware=False, nms="hard", sigma=0.5, camera=None, cone_model=None,
-                 pnp_iters=30):
-        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, class_aware, nms, sigma)
+                 pnp_iters=30, track=None):
+        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, class_aware, nms, sigma, track)
         self._init_pose(camera, cone_model, pnp_iters)
         self.keypoint_net = keypoint_net
         self.max_cones, self.bucket = int(max_cones), int(bucket)
@@ -705,8 +742,8 @@ class TiledFrameDetector(_Tiled, FrameDetector):
     _result_type = TiledFrameDetections
 
     def __init__(self, model, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0), batch_size=16,
-                 tile_batch=32, contain_thres=None, class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5):
-        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, nms=nms, sigma=sigma)
+                 tile_batch=32, contain_thres=None, class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5, track=None):
+        super().__init__(model, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, nms=nms, sigma=sigma, track=track)
         self._init_tiles(scale, tile_batch, contain_thres, class_aware, tile_merge)
 
     def _plan(self, sizes, first):
@@ -721,9 +758,9 @@ class TiledFrameConeDetector(_Tiled, FrameConeDetector):
 
     def __init__(self, model, keypoint_net, scale, conf_thres=None, nms_thres=None, top_k=200, max_boxes=200, outline=(255, 0, 0),
                  batch_size=16, max_cones=64, bucket=64, colours=KPT_COLOURS_RGB, tile_batch=32, contain_thres=None, class_aware=False,
-                 tile_merge="agnostic", nms="hard", sigma=0.5, camera=None, cone_model=None, pnp_iters=30):
+                 tile_merge="agnostic", nms="hard", sigma=0.5, camera=None, cone_model=None, pnp_iters=30, track=None):
         super().__init__(model, keypoint_net, conf_thres, nms_thres, top_k, max_boxes, outline, batch_size, max_cones, bucket, colours,
-                         nms=nms, sigma=sigma, camera=camera, cone_model=cone_model, pnp_iters=pnp_iters)
+                         nms=nms, sigma=sigma, camera=camera, cone_model=cone_model, pnp_iters=pnp_iters, track=track)
         self._init_tiles(scale, tile_batch, contain_thres, class_aware, tile_merge)
 
     def _plan(self, sizes, first):
@@ -747,6 +784,13 @@ def _save(annotated, path):
     return path
 
 
+def _print_tracks(name, res):
+    """with `track`: one line per box, its track id (a confirmed track's without brackets) beside the box"""
+    if res.track_id is not None:
+        for box, tid, ok in zip(res.boxes, res.track_id, res.confirmed):
+            print(f"{name}: track {tid if ok else '(%d)' % tid}  box " + " ".join(f"{v:.1f}" for v in box))
+
+
 def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, contain_thres=None, tile_merge="agnostic", **kw):
     """`device` is where the reference moves its input (detect.py:78) and where the caller has put the model (detect.py:51): the batches
     are built on the model's device, so the two must be the same GPU.  None: the model's device.  `tiles`: a TiledFrameDetector at
@@ -766,31 +810,33 @@ def _detector(model, device, conf_thres, nms_thres, tiles=False, scale=1.0, cont
 
 
 def single_img_detect(target_path, output_path, mode, model, device, conf_thres, nms_thres, *, tiles=False, scale=1.0, contain_thres=None,
-                      class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5):
+                      class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5, track=None):
     """detect.py:60-111 for one RGB image file: mode 'image' saves under `output_path` with the file's own name, any other mode saves over
     `target_path` (the reference's rule for its dumped video frames); the saved path is returned.  With no detection the image is
     saved unannotated.  `device` must be the GPU the model is on (or None).  Each call builds its own detector: for many files use `detect`
     on their directory.  Keyword-only `tiles=True`: tile-and-scale inference at `scale` (TiledFrameDetector), the counterpart of training
     with ts=True; the defaults are the reference's whole-frame pad and resize.  `class_aware`: FrameDetector's; with tiles it needs
     `tile_merge="per_class"` (TiledFrameDetector's).  `nms`, `sigma`: FrameDetector's; with tiles a soft method needs
-    `tile_merge="soft"` (class_aware=True: "soft_per_class")."""
+    `tile_merge="soft"` (class_aware=True: "soft_per_class").  `track`: FrameDetector's; the one frame's ids are printed beside its boxes."""
     check_tile_merge("single_img_detect", tiles, class_aware, tile_merge)
     check_nms("single_img_detect", tiles, nms, sigma, tile_merge)
     frame = _open_rgb(target_path)
     det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=1, class_aware=class_aware,
-                    nms=nms, sigma=sigma)
+                    nms=nms, sigma=sigma, track=track)
     res = next(iter(det.detect_frames([frame])))
+    _print_tracks(target_path, res)
     if mode == "image":
         return _save(res.annotated, os.path.join(output_path, target_path.split("/")[-1]))
     return _save(res.annotated, target_path)
 
 
 def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch_size=16, *, tiles=False, scale=1.0, contain_thres=None,
-           class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5):
+           class_aware=False, tile_merge="agnostic", nms="hard", sigma=0.5, track=None):
     """detect.py:113-196.  An image file (.jpg / .jpeg / .png / .tif) goes through `single_img_detect`; a directory has its image files,
     sorted by name, detected in batches of `batch_size` and written to `output_path` under their own names (-> the list of paths).
     Video containers need cv2 for decode and encode: ValueError; feed decoded frames to `FrameDetector.detect_frames` instead.
-    Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`, `tile_merge`, `nms`, `sigma`: as in `single_img_detect`."""
+    Keyword-only `tiles`, `scale`, `contain_thres`, `class_aware`, `tile_merge`, `nms`, `sigma`: as in `single_img_detect`.  `track`
+    (True or a TrackConfig): the directory's files, in name order, are one sequence; every box is printed with its track id."""
     check_tile_merge("detect", tiles, class_aware, tile_merge)
     check_nms("detect", tiles, nms, sigma, tile_merge)
     ext = os.path.splitext(target_path)[-1].lower()
@@ -799,9 +845,12 @@ def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch
                        if os.path.splitext(f)[-1].lower() in IMG_FORMATS and os.path.isfile(os.path.join(target_path, f)))
         print(f"Detection Mode is: directory ({len(names)} images)")
         det = _detector(model, device, conf_thres, nms_thres, tiles, scale, contain_thres, tile_merge, batch_size=batch_size,
-                        class_aware=class_aware, nms=nms, sigma=sigma)
+                        class_aware=class_aware, nms=nms, sigma=sigma, track=track)
         frames = (_open_rgb(os.path.join(target_path, f)) for f in names)
-        paths = [_save(res.annotated, os.path.join(output_path, f)) for f, res in zip(names, det.detect_frames(frames))]
+        paths = []
+        for f, res in zip(names, det.detect_frames(frames)):
+            _print_tracks(f, res)
+            paths.append(_save(res.annotated, os.path.join(output_path, f)))
         print(f"Please check output images at {output_path}")
         return paths
     if ext in VID_FORMATS:
@@ -813,6 +862,6 @@ def detect(target_path, output_path, model, device, conf_thres, nms_thres, batch
     print("Detection Mode is: image")
     path = single_img_detect(target_path=target_path, output_path=output_path, mode="image", model=model, device=device,
                              conf_thres=conf_thres, nms_thres=nms_thres, tiles=tiles, scale=scale, contain_thres=contain_thres,
-                             class_aware=class_aware, tile_merge=tile_merge, nms=nms, sigma=sigma)
+                             class_aware=class_aware, tile_merge=tile_merge, nms=nms, sigma=sigma, track=track)
     print(f"Please check output image at {path}")
     return path
